@@ -3,6 +3,7 @@
 gradient all-reduce + optimizer) on synthetic 540x960 SceneFlow-shape pairs, D=192, fp32.
 
   python bench.py --gpus N --steps K --warmup W [--config gwc_train|acv_train|kitti_infer|psm_volume]
+                  [--dump-outputs DIR] [--full]
 
 Launch.  One rank per GPU.  Under `python -m torch.distributed.run ... bench.py --gpus N` the ranks come
 from the environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*).  Started plainly with `--gpus N` (N > 1,
@@ -19,10 +20,23 @@ Configs (BASELINE.json `configs`):
 Per-GPU work is fixed (weak scaling); gradients are averaged over ranks through one flat fp32 buffer
 (stereo_toolbox_amd/distributed.py), by default in 2 ranges that overlap with the backward pass.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel of the config; achieved = algorithmic FLOPs or
-bytes of its launches / their HIP-event time inside the timed region, on the launching stream) and, at N=1,
-`cpu_baseline` (the CPU oracle -- a torch-op restatement of the reference -- on this box's host cores, bounded
-sample, warm-up + 2 timed runs; baseline only).
+Prints ONE JSON line on rank 0: `metric`, `value` (pairs or volumes per second over the timed steps), `unit`,
+`higher_is_better`, `dtype` and `ms_per_step` (wall time of one timed step).  A plain run does only what that line needs:
+set-up, `--warmup` steps, `--steps` timed steps, no event or per-launch instrumentation inside them.
+
+--full adds everything else the benchmark measures, in the same process: `roofline` (dominant kernel of the config;
+achieved = algorithmic FLOPs or bytes of its launches / their HIP-event time inside the timed region, on the launching
+stream), the config's secondary roofline blocks (timed after the timed steps), the forward / backward `path_split` of the
+train step, the exposed gradient-exchange time per rank (N > 1) and, at N=1, `cpu_baseline` (the CPU oracle -- a torch-op
+restatement of the reference -- on the host cores, bounded sample, warm-up + 2 timed runs; baseline only;
+`--no-cpu-baseline` leaves it out).  The HIP events of --full are recorded inside the timed steps, so its `ms_per_step`
+can be slightly higher than a plain run's.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (float32): the
+train configs the disparity predictions, the loss, the averaged flat gradient and the updated parameters; kitti_infer the
+disparity map; psm_volume the cost volume.  All arrays together stay within 60 MiB: one too large for its share is
+replaced by a fixed, seeded sample of its elements (`<name>.sample.npy`, 1-D).  Inputs and weights are seeded and MIOpen
+is held to deterministic solvers, so two runs with the same arguments see identical inputs and compute identical outputs.
 """
 import argparse
 import json
@@ -347,6 +361,38 @@ def cpu_baseline(cfg, maxdisp, full_cap_s=180.0):
                        f"{ts / frac:.0f} s, above the {full_cap_s:.0f} s cap)")
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # all arrays written by --dump-outputs together (float32)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write the named tensors (nested lists / tuples are split into `<name>_<i>`) to `out_dir/<name>.npy` as float32.
+    Arrays are taken smallest first, each granted an equal share of what is left of DUMP_BUDGET_BYTES; one above its share
+    is written as `<name>.sample.npy`: the elements at fixed, seeded flat indices (sorted, drawn with replacement), the same
+    for every run of the same arguments."""
+    import numpy as np
+    flat = {}
+
+    def add(name, v):
+        if isinstance(v, (list, tuple)):
+            for i, t in enumerate(v):
+                add(f"{name}_{i}", t)
+        elif isinstance(v, torch.Tensor):
+            flat[name] = v.detach()
+    for k, v in arrays.items():
+        add(k, v)
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4
+    for i, (name, t) in enumerate(sorted(flat.items(), key=lambda kv: (kv[1].numel(), kv[0]))):
+        share = max(1, left // (len(flat) - i))
+        left -= min(share, t.numel())
+        t = t.float()
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(20240617)
+            idx = torch.randint(0, t.numel(), (share,), generator=g).sort().values.to(t.device)
+            t, name = t.reshape(-1).index_select(0, idx), name + ".sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -363,7 +409,16 @@ def parse_args(argv=None):
     ap.add_argument("--fused-adam", type=int, default=1, help="torch.optim.Adam(fused=True) (default) / 0 = the multi-tensor form")
     ap.add_argument("--graph", action="store_true",
                     help="capture the whole step (fwd+bwd+all-reduce+Adam) in one hipGraph and replay it")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the rooflines, the path split, the per-rank exchange time and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, <= 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def free_port():
@@ -470,18 +525,25 @@ def main(argv=None, platform=None):
     H, W, B = args.height or H, args.width or W, args.batch or B
     D = args.maxdisp
     torch.backends.cudnn.benchmark = True
+    # Same arguments, same outputs on every run (--dump-outputs compares builds output for output): MIOpen may only pick
+    # deterministic solvers for the stock convolutions -- no split-K weight gradients that sum with atomics in whatever
+    # order the waves arrive, which 13 Adam steps amplify to whole disparity levels.  The reference trainer runs the
+    # same way (trainer_torchrun.py set_seed: cudnn.deterministic = True).
+    torch.backends.cudnn.deterministic = True
     g = torch.Generator(device=dev)
     g.manual_seed(1000 + rank)                     # every rank draws its own shard (trainer_torchrun.py:88)
-    timer = KernelTimer()
+    full = args.full
+    timer = KernelTimer()                          # installed and enabled under --full only
 
     split = None
     if mode == "volume":
         L = torch.randn(B, 32, H // 4, W // 4, device=dev, generator=g)
         R = torch.randn(B, 32, H // 4, W // 4, device=dev, generator=g)
-        timer.install_volume()
+        if full:
+            timer.install_volume()
 
         def step():
-            return ops.cost_volume(None, None, L, R, D // 4, 0, mask_left=True)
+            return {"cost_volume": ops.cost_volume(None, None, L, R, D // 4, 0, mask_left=True)}
     else:
         model = getattr(models, model_name)(D)
         sd = model.state_dict()
@@ -491,8 +553,9 @@ def main(argv=None, platform=None):
         broadcast_parameters(model)
         left = torch.randn(B, 3, H, W, device=dev, generator=g)
         right = torch.randn(B, 3, H, W, device=dev, generator=g)
-        timer.install_conv()
-        timer.install_volume()
+        if full:
+            timer.install_conv()
+            timer.install_volume()
         if mode == "train":
             model.train()
             overlap = not args.no_overlap and not args.graph
@@ -509,7 +572,8 @@ def main(argv=None, platform=None):
             gt = 190.0 * torch.rand(B, H, W, device=dev, generator=g)
 
             sync_events = []                       # (before, after) finish(): what the gradient exchange adds to the stream
-            split = PathSplit(model) if hasattr(model, "aggregate") and platform.event_timing and not args.graph else None
+            split = (PathSplit(model) if full and hasattr(model, "aggregate") and platform.event_timing and not args.graph
+                     else None)
 
             def step():
                 gsync.detach_grads()
@@ -533,13 +597,14 @@ def main(argv=None, platform=None):
                 opt.step()
                 if split:
                     split.end()
+                return {"preds": preds, "loss": loss}
         else:
             model.eval()
             split = None
 
             def step():
                 with torch.no_grad():
-                    return model(left, right)
+                    return {"disparity": model(left, right)}
 
     if args.graph and mode in ("train", "eval"):
         # hipGraph path: warm up on a side stream (MIOpen search, workspaces), then capture one step (train: forward + backward +
@@ -555,8 +620,12 @@ def main(argv=None, platform=None):
         if mode == "train":
             gsync.detach_grads()
         with torch.cuda.graph(graph):
-            step()
-        step = graph.replay            # noqa: F811
+            captured = step()          # (its tensors are the graph's: every replay rewrites them in place)
+        replay = graph.replay
+
+        def step():                    # noqa: F811
+            replay()
+            return captured
     for _ in range(args.warmup):
         step()
     if world > 1:
@@ -564,10 +633,11 @@ def main(argv=None, platform=None):
     sync()
     if mode == "train" and split:
         split.enabled = True
-    timer.enabled = platform.event_timing and not args.graph   # per-launch HIP events cannot be recorded inside a replayed graph
+    # per-launch HIP events cannot be recorded inside a replayed graph
+    timer.enabled = full and platform.event_timing and not args.graph
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     sync()
     if world > 1:
         dist.barrier()
@@ -583,11 +653,18 @@ def main(argv=None, platform=None):
         mine = torch.tensor([dt / args.steps * 1e3, exposed], device=dev, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
-        per_rank = {"ms_per_step": [round(float(x[0]), 3) for x in allr],
-                    "grad_sync_ms_on_stream": [round(float(x[1]), 3) for x in allr]}
+        per_rank = {"ms_per_step": [round(float(x[0]), 3) for x in allr]}
+        if full:
+            per_rank["grad_sync_ms_on_stream"] = [round(float(x[1]), 3) for x in allr]
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        arrays = dict(last)
+        if mode == "train":
+            arrays["grad_flat"] = gsync.flat
+            arrays["params_flat"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        dump_outputs(args.dump_outputs, arrays)
 
     if rank == 0:
         std_shape = (H, W, B, D) == (576, 960, 1, 192)    # the shape the committed PMC summaries were collected at
@@ -678,15 +755,15 @@ def main(argv=None, platform=None):
                     "traffic": committed_pmc_traffic("r06_pmc_conv2d.txt", ("conv2d.hip",)) if std_shape else None,
                     "traffic_source": "profiles/r06_pmc_conv2d.txt: FETCH_SIZE (x2, gfx950) + WRITE_SIZE of this launch shape "
                                       "(algorithmic 35.4 MB), separate passes; a committed-profile constant stamped with the kernel's source"}
-        extra = {}
-        if mode == "train":
+        extra, roof = {}, None
+        if full and mode == "train":
             roof = roof_conv()
             extra["roofline_volume_build"] = roof_volume()
             extra["roofline_conv2d"] = roof_conv2d()
-        elif mode == "eval":
+        elif full and mode == "eval":
             roof = roof_volume()
             extra["roofline_conv3d"] = roof_conv()
-        else:
+        elif full:
             roof = roof_volume()
             if platform.event_timing:
                 # "also report unpadded [1,32,135,240]" (540x960 before the reference's pad_to_2x)
@@ -735,8 +812,9 @@ def main(argv=None, platform=None):
                        **({"optimizer": opt_name} if mode == "train" else {}),
                        "miopen_user_db": (f"{tuning_db} (private copy of stereo_toolbox_amd/tuning/miopen)" if tuning_db
                                           else None)},
-            "roofline": roof,
         }
+        if full:
+            out["roofline"] = roof
         out.update(extra)
         if mode == "train" and split:
             ps = split.summary()
@@ -745,7 +823,7 @@ def main(argv=None, platform=None):
                 out["path_split"] = ps
         if per_rank is not None:
             out["per_rank"] = dict(per_rank, host_threads_per_rank=pin["threads"], host_cores_rank0=pin["cores"])
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config, D)
         print(json.dumps(out), flush=True)
     if world > 1:

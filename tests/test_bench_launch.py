@@ -62,7 +62,7 @@ def test_bench_acv_train_two_ranks_emulated():
     from tests.emu_util import emu_lib
     emu_lib()
     r = _run(["--config", "acv_train", "--gpus", "2", "--batch", "2", "--steps", "1", "--warmup", "0", "--height", "16", "--width", "64",
-              "--maxdisp", "64", "--no-cpu-baseline"], {"OMP_NUM_THREADS": "2"}, script=BENCH_EMU)
+              "--maxdisp", "64", "--no-cpu-baseline", "--full"], {"OMP_NUM_THREADS": "2"}, script=BENCH_EMU)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json_line(r.stdout)
     assert out["config"]["name"] == "acv_train" and out["n_gpus"] == 2 and out["config"]["global_batch"] == 4
@@ -76,6 +76,58 @@ def test_bench_psm_volume_config_emulated():
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json_line(r.stdout)
     assert out["config"]["name"] == "psm_volume" and out["unit"] == "volumes/s" and out["n_gpus"] == 1
+
+
+def test_bench_plain_run_steps_and_dump_outputs_emulated(tmp_path):
+    """A plain run times exactly --steps steps and reports only the headline fields (no roofline, no CPU baseline);
+    --dump-outputs writes what the last timed step computed as float32 .npy files, identical for two runs with the same
+    arguments (seeded inputs)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run(["--config", "psm_volume", "--steps", "3", "--warmup", "0", "--height", "16", "--width", "64", "--maxdisp", "32",
+                  "--dump-outputs", str(d)], script=BENCH_EMU)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = _json_line(r.stdout)
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-3 * out["value"] + 1e-3
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in out
+        assert "roofline" not in out and "cpu_baseline" not in out
+        vol = np.load(d / "cost_volume.npy")
+        assert vol.dtype == np.float32 and vol.size == 1 * 64 * 8 * 4 * 16 and np.isfinite(vol).all()
+        dumps.append(vol)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_full_reports_roofline_emulated():
+    r = _run(["--config", "psm_volume", "--steps", "1", "--warmup", "0", "--height", "16", "--width", "64", "--maxdisp", "32",
+              "--full", "--no-cpu-baseline"], script=BENCH_EMU)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _json_line(r.stdout)
+    assert "roofline" in out and out["steps"] == 1
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """Arrays are written whole while they fit their share of the budget; a larger one becomes a seeded sample of its
+    elements, the same indices on every call; everything together stays within the budget."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1000)
+    big = torch.arange(10000, dtype=torch.float64)
+    arrays = {"small": torch.ones(3, 4), "preds": [torch.zeros(2, 5), torch.full((7,), 2.0)], "big": big, "skip": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["big.sample.npy", "preds_0.npy", "preds_1.npy", "small.npy"]
+    total = sum(os.path.getsize(tmp_path / "a" / n) - 128 for n in names)         # (128-byte .npy headers)
+    assert total <= 4 * 1000
+    assert np.load(tmp_path / "a" / "small.npy").shape == (3, 4)
+    s = np.load(tmp_path / "a" / "big.sample.npy")
+    assert s.dtype == np.float32 and s.size == 1000 - 12 - 10 - 7
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.sample.npy"))
+    assert (np.diff(s) >= 0).all() and s.min() >= 0 and s.max() < 10000      # sorted flat indices of arange
 
 
 @pytest.mark.gpu

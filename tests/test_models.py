@@ -460,11 +460,19 @@ def test_acvnet_eval_parity(env, flags):
 
 
 def test_acvnet_train_parity(emu_env, parity_log):
-    """Whole ACVNet train step on the emulator against the live oracle; GPU twin: test_acvnet_toy_train_step_parity."""
+    """Whole ACVNet train step on the emulator against the live oracle; GPU twin: test_acvnet_toy_train_step_parity.
+    BatchNorm betas shifted by +1 as in the GPU twins: with betas of +-0.1 this 16x64 step sits on ReLU kinks, and the 2-D
+    kernel's fp32 summation order (csrc/conv2d.hip, which the feature CNN's 3x3 layers use since round 6) flips activations
+    that the oracle's convolutions -- the same ops as its fp64 run -- do not, so the fp32-oracle distance no longer measures
+    the step's conditioning (2.6e-2 of a tensor's max against 1.6e-5 with the shift, same tolerances)."""
     from stereo_toolbox_amd.models import ACVNet
     env = emu_env
     H, W, D, B = _acv_shape(env)
-    m, sd = _filled(ACVNet, D)
+    m = ACVNet(D)
+    sd = m.state_dict()
+    fill_state_dict(sd, bn_beta_shift=1.0)
+    m.load_state_dict(sd)
+    sd = {k: v.clone() for k, v in sd.items()}
     m = m.to(env.device).train()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
     gt = synthetic_tensor((B, H, W), 3, lo=0.0, hi=float(D - 2))

@@ -92,28 +92,37 @@ def test_estimators_and_head():
     close(O.regression_head(cost, 16, 20, 28), g["head"], 1e-6)
 
 
+def _ulps(a, b, n=4):
+    """|a - b| within n fp32 ulps of b's largest magnitude: the vectorised CPU reductions of torch sum in an order that
+    depends on the host's SIMD width, so a fixture recorded on one x86 host is 1-2 ulps off on another (measured: 3.8e-6 at
+    disparities of ~30, i.e. two ulps)."""
+    err = (a - b).abs().max().item()
+    assert err <= n * 2.0 ** -23 * b.abs().max().item(), err
+
+
 def test_modal_estimators():
-    """unimodal / dominant-modal estimators: bitwise against the reference's outputs
+    """unimodal / dominant-modal estimators: against the reference's outputs within a few fp32 ulps
     (tests/golden/make_golden_modal.py)."""
     from stereo_toolbox_amd.utils import synthetic_modal_volume
     g = load("estimators_modal.npz")
     for tag, (B, D, H, W, seed) in {"a": (2, 32, 5, 9, 21), "b": (1, 48, 4, 7, 22), "c": (1, 192, 3, 5, 23)}.items():
         x = synthetic_modal_volume(B, D, H, W, seed)
-        assert torch.equal(O.unimodal_disparity_estimator(x, D), g[f"uni_{tag}"])
-        assert torch.equal(O.dominant_modal_disparity_estimator(x, D), g[f"dom_{tag}"])
+        _ulps(O.unimodal_disparity_estimator(x, D), g[f"uni_{tag}"])
+        _ulps(O.dominant_modal_disparity_estimator(x, D), g[f"dom_{tag}"])
     peaky = torch.softmax(synthetic_tensor((2, 16, 6, 10), 13) * 4, 1)
-    assert torch.equal(O.unimodal_disparity_estimator(peaky, 16), g["uni_peaky"])
-    assert torch.equal(O.dominant_modal_disparity_estimator(peaky, 16), g["dom_peaky"])
-    # split_mode (loss_functions/split_mode.py): mode and boolean mask, bitwise
+    _ulps(O.unimodal_disparity_estimator(peaky, 16), g["uni_peaky"])
+    _ulps(O.dominant_modal_disparity_estimator(peaky, 16), g["dom_peaky"])
+    # split_mode (loss_functions/split_mode.py): boolean mask bitwise, mode within a few fp32 ulps
     import numpy as np
     cases = {"a": (2, 32, 5, 9, 21), "b": (1, 48, 4, 7, 22), "c": (1, 192, 3, 5, 23)}
     for tag, (B, D, H, W, seed) in cases.items():
         mode, mask = O.split_mode(synthetic_modal_volume(B, D, H, W, seed), D)
-        assert mask.dtype == torch.bool and torch.equal(mode, g[f"split_mode_{tag}"])
+        assert mask.dtype == torch.bool
+        _ulps(mode, g[f"split_mode_{tag}"])
         want = np.unpackbits(g[f"split_mask_{tag}"].numpy())[:mask.numel()].reshape(mask.shape)
         assert np.array_equal(mask.numpy(), want.astype(bool))
     mode, mask = O.split_mode(peaky, 16)
-    assert torch.equal(mode, g["split_mode_peaky"])
+    _ulps(mode, g["split_mode_peaky"])
     assert np.array_equal(mask.numpy(), np.unpackbits(g["split_mask_peaky"].numpy())[:mask.numel()].reshape(mask.shape).astype(bool))
     # gradients w.r.t. the volume (constant mode mask): oracle autograd vs the reference's
     for tag, (B, D, H, W, seed) in {"a": (2, 32, 5, 9, 21), "b": (1, 48, 4, 7, 22)}.items():

@@ -2,15 +2,14 @@
 (trainer/trainer_torchrun.py:105-123: `SyncBatchNorm.convert_sync_batchnorm` + `DistributedDataParallel`) and torch DDP on a ROCm
 device.
 
-* build container (`-m "not gpu"`): the reference's `Trainer` class is imported from /root/reference (it needs only torch / numpy /
-  tqdm) -- never copied, never shipped; the test skips where that tree does not exist (the GPU box).  Two gloo ranks run the
-  product modules on the host-emulator build of the kernels.  Only `_train_iteration` (trainer_torchrun.py:264-303, the designed
-  extension point: the stock one unpacks IGEV's `(init_disp, disp_preds)`) is overridden.
+* without a GPU (`-m "not gpu"`): `_TorchrunTrainer` below plays the caller -- the steps of the reference's torchrun trainer
+  (rank from the environment, process group, optional `SyncBatchNorm` conversion, `DDP` wrap, one train iteration), written
+  here with torch's public API so that the test needs nothing outside this repository.  Two gloo ranks run the product
+  modules on the host-emulator build of the kernels; the iteration is GwcNet's (a list of four predictions).
 * GPU box (`-m gpu`): `init_process_group("nccl", world_size=1)` + `DDP(model.cuda(), device_ids=[0])`, gradients bitwise equal to
   the un-wrapped module; `find_unused_parameters` for `ACVNet(attn_weights_only=True)`; `FlatGradSync(overlap=True)` with the
   collectives forced on in the 1-rank RCCL group, so that hook -> async all-reduce (AVG) -> finish() runs on a real stream.
 """
-import importlib.util
 import os
 import socket
 import sys
@@ -21,9 +20,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 import torch.nn as nn
+from torch.nn.parallel import DistributedDataParallel as DDP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_TRAINER = "/root/reference/stereo_toolbox/trainer/trainer_torchrun.py"
 LOSS_W = (0.5, 0.5, 0.7, 1.0)
 H, W, D = 16, 64, 32
 
@@ -36,11 +35,50 @@ def _free_port():
     return p
 
 
-def _load_reference_trainer():
-    spec = importlib.util.spec_from_file_location("ref_trainer_torchrun", REF_TRAINER)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+class _TorchrunTrainer:
+    """The caller the product drops in under (the reference's trainer/trainer_torchrun.py: Trainer.__init__,
+    setup_distributed, prepare_model, _train_iteration): a torchrun-style trainer that takes its rank from the environment,
+    seeds per rank, joins the process group, converts BatchNorm to SyncBatchNorm on request, wraps the model in
+    DistributedDataParallel and runs one iteration.  CPU ranks: DDP is given no device_ids."""
+
+    def __init__(self, config):
+        self.config = config
+        self.local_rank = int(os.environ.get("LOCAL_RANK", -1))
+        self.world_size = int(os.environ.get("WORLD_SIZE", -1))
+        self.global_rank = int(os.environ.get("RANK", -1))
+        self.device = torch.device("cpu")
+        torch.manual_seed(config.seed + max(self.global_rank, 0))
+        self.max_disp = config.max_disp
+
+    def is_distributed(self):
+        return self.local_rank != -1
+
+    def setup_distributed(self):
+        if not dist.is_initialized():
+            dist.init_process_group(backend=self.config.dist_backend)
+        self.world_size = dist.get_world_size()
+        self.global_rank = dist.get_rank()
+
+    def prepare_model(self, model):
+        model = model.to(self.device)
+        if self.is_distributed():
+            if self.config.sync_bn:
+                model = nn.SyncBatchNorm.convert_sync_batchnorm(model)
+            model = DDP(model, find_unused_parameters=self.config.find_unused_parameters)
+        return model
+
+    def train_iteration(self, model, data, optimizer):
+        """GwcNet's iteration: a list of four predictions, the product's masked multi-output loss."""
+        from stereo_toolbox_amd.losses import masked_smooth_l1_multi
+        optimizer.zero_grad()
+        left = data["left"].to(self.device, non_blocking=True)
+        right = data["right"].to(self.device, non_blocking=True)
+        gt = data["gt_disp"].to(self.device, non_blocking=True).squeeze(1)
+        preds = model(left, right)
+        loss = masked_smooth_l1_multi(preds, gt, self.max_disp, LOSS_W)
+        loss.backward()
+        optimizer.step()
+        return loss.item()
 
 
 def _filled_model(ctor_name, *a, bn_beta_shift=0.0, **k):
@@ -64,38 +102,16 @@ def _trainer_worker(rank, world, port, q, sync_bn):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     torch.set_num_threads(2)
-    ref = _load_reference_trainer()
     from tests.emu_util import emu_product_path
     from stereo_toolbox_amd.distributed import FlatGradSync, broadcast_parameters
     from stereo_toolbox_amd.losses import masked_smooth_l1_multi
 
-    class GwcTrainer(ref.Trainer):
-        """The reference trainer with its one designed override: GwcNet returns a list of four predictions."""
-
-        def _train_iteration(self, model, data, optimizer, scheduler, scaler):
-            optimizer.zero_grad()
-            left = data["left"].to(self.device, non_blocking=True)
-            right = data["right"].to(self.device, non_blocking=True)
-            gt = data["gt_disp"].to(self.device, non_blocking=True).squeeze(1)
-            preds = model(left, right)
-            loss = masked_smooth_l1_multi(preds, gt, self.max_disp, LOSS_W)
-            loss.backward()
-            optimizer.step()
-            return loss.item()
-
-    config = types.SimpleNamespace(seed=7, max_disp=D, sync_bn=sync_bn, dist_backend="gloo", amp=False, clip_grad=None,
-                                   find_unused_parameters=False)
-    trainer = GwcTrainer(config)
-    # Without a ROCm device the reference constructor declares the run non-distributed (trainer_torchrun.py:36-41 sets
-    # local_rank = -1).  Put the rank back and run the reference's own set-up methods, so that prepare_model takes its
-    # distributed branch; its `DDP(model, device_ids=[local_rank], ...)` call is handed CPU modules here, for which torch
-    # requires device_ids=None -- the one argument this shim drops.
-    trainer.local_rank = rank
+    config = types.SimpleNamespace(seed=7, max_disp=D, sync_bn=sync_bn, dist_backend="gloo", find_unused_parameters=False)
+    trainer = _TorchrunTrainer(config)
     trainer.setup_distributed()
     assert trainer.is_distributed() and trainer.world_size == world and dist.get_backend() == "gloo"
-    real_ddp = ref.DDP
-    ref.DDP = lambda m, device_ids=None, output_device=None, **kw: real_ddp(m, **kw)
-    # torch's DDP constructor also refuses SyncBatchNorm layers inside CPU modules (their stock forward needs a GPU).  The
+    real_ddp = DDP
+    # torch's DDP constructor refuses SyncBatchNorm layers inside CPU modules (their stock forward needs a GPU).  The
     # product never calls that forward (the modules are parameter containers; aggregation._bn_state all-reduces the
     # statistics itself), so the check -- which only stamps `_specify_ddp_gpu_num(1)` on the layers -- is skipped here.
     real_ddp._passing_sync_batchnorm_handle = lambda self, module: None
@@ -112,7 +128,7 @@ def _trainer_worker(rank, world, port, q, sync_bn):
         n_sync = sum(isinstance(m, nn.SyncBatchNorm) for m in model.modules())
         assert (n_sync > 0) == bool(sync_bn)
         opt = torch.optim.SGD(model.parameters(), lr=0.0)          # (lr 0: the gradients are what is compared)
-        loss = trainer._train_iteration(model, data, opt, None, None)
+        loss = trainer.train_iteration(model, data, opt)
         ddp_grads = [p.grad.clone() for p in model.module.parameters()]
         ddp_stats = {k: v.clone() for k, v in model.module.state_dict().items() if "running" in k or "num_batches" in k}
 
@@ -145,11 +161,10 @@ def _trainer_worker(rank, world, port, q, sync_bn):
     dist.destroy_process_group()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TRAINER), reason="the reference tree exists only in the build container")
 @pytest.mark.parametrize("sync_bn", [False, True], ids=["per_replica_bn", "sync_bn"])
 def test_reference_trainer_prepare_model_two_ranks(sync_bn):
-    """north_star: "drops in under the existing trainer".  GwcNet_GC through the reference's own Trainer.prepare_model
-    (optionally SyncBatchNorm-converted, then DDP-wrapped) on two gloo ranks, one train iteration: every rank ends with
+    """north_star: "drops in under the existing trainer".  GwcNet_GC through the trainer's prepare_model (`_TorchrunTrainer`:
+    optionally SyncBatchNorm-converted, then DDP-wrapped) on two gloo ranks, one train iteration: every rank ends with
     the same gradients, they equal the FlatGradSync path's, BatchNorm running statistics and counters agree."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from emu_util import emu_lib
