@@ -324,6 +324,45 @@ int stx_disparity_variance_fwd(const float* x, const float* disp, const float* s
 int stx_disparity_variance_bwd(const float* g, const float* x, const float* disp, const float* samples, float* gx, float* gdisp,
                                float* gsamples, int B, int D, int HW, void* stream);
 
+/* ---- geo_lookup.hip: geometry-encoding lookup and convex upsampling of the IGEV family ---------------------------------
+ * Combined_Geo_Encoding_Volume (models/IGEVStereo/geometry.py:7-70; called once per GRU iteration, igev_stereo.py:229-239) and
+ * context_upsample (models/IGEVStereo/submodule.py:243-255; igev_stereo.py:164,254).
+ * PYRAMIDS are pixel-major, the levels one behind the other in one buffer: level i of a pyramid over `rows` rows of `len`
+ * positions with C channels is [rows][len >> i][C] (avg_pool2d([1,2]) of level i-1 along `len`, an odd tail dropped) and the
+ * whole pyramid has stx_geo_pyramid_floats(rows, len, C, levels) floats.  Geometry pyramid: rows = B*H*W pixels, len = D;
+ * correlation pyramid: rows = B*H*W1, len = W2, C = 1.  levels 1..3.
+ * stx_geo_corr_fwd: all-pairs row correlation corr[b][h][w1][w2] = sum_c fmap1[b][c][h][w1] * fmap2[b][c][h][w2]
+ *   (geometry.py:62-70) on the matrix cores AND its pooled levels, into cpyr; fmap1 [B][C][H][W1], fmap2 [B][C][H][W2], any C.
+ * stx_geo_corr_bwd: gcpyr (gradient of every level) -> gfmap1, gfmap2 (either may be NULL); every element written.
+ * stx_geo_pyramid_fwd: vol dense [B][D][H][W][C] (C % 4 == 0) -> gpyr, all levels in one launch; _bwd: the inverse, gvol
+ *   fully written.  D * 17 * C floats must fit 64 KiB of LDS at a tile of 16 pixels (narrower tiles are used beyond that). */
+long long stx_geo_pyramid_floats(long long rows, int len, int C, int levels);
+int stx_geo_corr_fwd(const float* fmap1, const float* fmap2, float* cpyr, int B, int C, int H, int W1, int W2, int levels,
+                     void* stream);
+int stx_geo_corr_bwd(const float* gcpyr, const float* fmap1, const float* fmap2, float* gfmap1, float* gfmap2, int B, int C, int H,
+                     int W1, int W2, int levels, void* stream);
+int stx_geo_pyramid_fwd(const float* vol, float* gpyr, int B, int D, int H, int W, int C, int levels, void* stream);
+int stx_geo_pyramid_bwd(const float* ggpyr, float* gvol, int B, int D, int H, int W, int C, int levels, void* stream);
+/* The lookup (geometry.py:35-59): disp, coords [B*H*W] (coords = the pixel's own column in the reference);
+ * out [B][levels * (C + 1) * (2 radius + 1)][H][W], per level first channel c * (2 radius + 1) + k for the C geometry channels
+ * sampled at disp / 2^i + k - radius, then the 2 radius + 1 samples of the pixel's correlation row at
+ * (coords - disp) / 2^i + k - radius; linear interpolation, taps outside the level read as zero.  radius 1..8; the
+ * correlation rows have W1 = W.
+ * _bwd: gout -> ADDED (+=) to ggpyr / gcpyr (either may be NULL), which the caller clears before the first of the lookups
+ * whose gradients it wants summed; a pixel touches only its own rows: no atomics, bitwise reproducible.  disp and coords
+ * carry no gradient (the reference detaches disp, igev_stereo.py:238). */
+int stx_geo_lookup_fwd(const float* gpyr, const float* cpyr, const float* disp, const float* coords, float* out, int B, int H,
+                       int W, int D, int C, int W2, int levels, int radius, void* stream);
+int stx_geo_lookup_bwd(const float* gout, const float* disp, const float* coords, float* ggpyr, float* gcpyr, int B, int H, int W,
+                       int D, int C, int W2, int levels, int radius, void* stream);
+/* context_upsample: disp_low [B][1][h][w], up_weights [B][9][4h][4w] -> out [B][4h][4w],
+ * out[4y+j][4x+i] = sum_t up_weights[t][4y+j][4x+i] * disp_low[y + t/3 - 1][x + t%3 - 1] (zero padding), no unfolded or
+ * up-sampled temporary.  _bwd: g [B][4h][4w] -> gdisp [B][1][h][w] (needs up_weights) and gweights [B][9][4h][4w] (needs
+ * disp_low); either may be NULL; deterministic. */
+int stx_context_upsample_fwd(const float* disp_low, const float* up_weights, float* out, int B, int h, int w, void* stream);
+int stx_context_upsample_bwd(const float* g, const float* disp_low, const float* up_weights, float* gdisp, float* gweights, int B,
+                             int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

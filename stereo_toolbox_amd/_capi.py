@@ -92,6 +92,16 @@ SIGNATURES = {
     "stx_disparity_variance_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "stx_sampled_volume_fwd": [_P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "stx_sampled_volume_bwd": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    # geo_lookup.hip
+    "stx_geo_pyramid_floats": [_L, _I, _I, _I],
+    "stx_geo_corr_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "stx_geo_corr_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "stx_geo_pyramid_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "stx_geo_pyramid_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "stx_geo_lookup_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "stx_geo_lookup_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "stx_context_upsample_fwd": [_P, _P, _P, _I, _I, _I, _P],
+    "stx_context_upsample_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

@@ -16,8 +16,9 @@ classes of 2x2x2 taps -- ops.embed_deconv4_weight) is on the MFMA kernels of csr
 volumes (GEMM-K in steps of 8, output columns in blocks of 32); BatchNorm3d + LeakyReLU(0.01) are activation code 3 of the
 fused BN passes (training) / of the convolution epilogue (inference); the FeatureAtt gate `sigmoid(att) * cv` is one
 streaming kernel (stx_gate_fwd / _bwd); volume, softmax and regression are the kernels of the rest of the package.  The 2-D
-side of FeatureAtt (two 1x1 Conv2d on the backbone features) is stock PyTorch, like every 2-D CNN here.  The 2-D backbone,
-the GRU updates and the geometry encoding of those models are out of scope.
+side of FeatureAtt (two 1x1 Conv2d on the backbone features) is stock PyTorch, like every 2-D CNN here.  The geometry
+encoding that consumes `geo_encoding_volume` is geometry.py; the 2-D backbone and the GRU updates of those models are out of
+scope.
 """
 import torch
 import torch.nn as nn

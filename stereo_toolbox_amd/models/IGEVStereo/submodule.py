@@ -2,8 +2,9 @@
 FoundationStereo's volume is a DIFFERENT function -- per-group cosine similarity -- and lives in models/FoundationStereo) on the HIP
 kernels -- drop-in functions of reference models/IGEVStereo/submodule.py plus the two lines of
 `IGEVStereo.forward` that sit on the hot path (igev_stereo.py:206 and :211-212).  The 3-D regularisation between them
-(`corr_stem`, `corr_feature_att`, `cost_agg` = hourglass(8), `classifier`) is in aggregation.py; the rest of those models
-(feature backbones, GRU updates, geometry encoding) is outside the scope of this package.
+(`corr_stem`, `corr_feature_att`, `cost_agg` = hourglass(8), `classifier`) is in aggregation.py, the geometry-encoding lookup
+of the GRU iterations (`Combined_Geo_Encoding_Volume`) in geometry.py, and `context_upsample` (submodule.py:243-255, the convex 4x upsampling of igev_stereo.py:164,254) below; the
+rest of those models (feature backbones, GRU updates) is outside the scope of this package.
 
     gwc_volume = build_gwc_volume(match_left, match_right, max_disp // 4, 8)      # 96 channels -> 8 groups of 12
     prob       = F.softmax(classifier(volume).squeeze(1), dim=1)
@@ -48,3 +49,10 @@ def init_disparity(cost, max_disp):
     c = cost.squeeze(1).contiguous()
     prob = _SoftmaxDFn.apply(c) if (torch.is_grad_enabled() and c.requires_grad) else ops.softmax_over_d(c)
     return disparity_regression(prob, max_disp // 4)
+
+
+def context_upsample(disp_low, up_weights):
+    """reference IGEVStereo/submodule.py:243-255: disp_low [B,1,h,w], up_weights [B,9,4h,4w] -> [B,4h,4w], every output pixel
+    the up_weights-weighted sum of the 3x3 low-resolution neighbourhood of its cell (zero padding); one fused kernel forward,
+    two backward (stx_context_upsample_fwd / _bwd), no unfolded or nearest-upsampled temporary."""
+    return ops.context_upsample(disp_low, up_weights)

@@ -1584,3 +1584,199 @@ def softmax_over_d(x):
     y = torch.empty_like(x)
     _call("stx_softmax_d_fwd", _p(x), _p(y), B, D, H * W)
     return y
+
+
+# --------------------------------------------------------------------------------------- IGEV geometry-encoding lookup
+def geo_pyramid_floats(rows, length, channels, levels):
+    """Floats of a pixel-major pyramid (include/stx_hip.h, geo_lookup.hip): level i is [rows][length >> i][channels]."""
+    n = int(get_lib().raw("stx_geo_pyramid_floats")(rows, length, channels, levels))
+    if n <= 0:
+        raise StxError(f"geometry pyramid: bad shape rows={rows} length={length} channels={channels} levels={levels}")
+    return n
+
+
+class _PyramidGrads:
+    """The gradient buffers of the two pyramids of one `Combined_Geo_Encoding_Volume`, shared by all of its lookups within
+    one backward pass: stx_geo_lookup_bwd ADDS into the rows a pixel owns, so the 22-32 lookups of a training step
+    accumulate in place and the pyramid-build node receives ONE gradient per pyramid (the lookup that runs first hands the
+    buffers to autograd, the others return nothing) instead of one dense pyramid-sized tensor per iteration."""
+
+    def __init__(self):
+        self.task, self.bufs = None, None
+
+    def take(self, n_geo, n_corr, device):
+        """(first lookup of this backward pass?, (ggpyr, gcpyr))"""
+        task = torch._C._current_graph_task_id()
+        first = self.bufs is None or task != self.task
+        if first:
+            self.task = task
+            self.bufs = (torch.zeros(n_geo, dtype=torch.float32, device=device),
+                         torch.zeros(n_corr, dtype=torch.float32, device=device))
+        return first, self.bufs
+
+    def release(self):
+        self.bufs = None
+
+
+class GeoPyramidFn(torch.autograd.Function):
+    """geometry.py:14-30: all-pairs row correlation (MFMA) with its pooled levels, and the pixel-major pyramid of the
+    geometry volume; vol dense [B, D, H, W, C], fmaps NCHW -> (gpyr, cpyr) flat buffers."""
+
+    @staticmethod
+    def forward(ctx, vol, f1, f2, levels, grads):
+        B, D, H, W, C = vol.shape
+        Cf, W2 = f1.shape[1], f2.shape[3]
+        gpyr = torch.empty(geo_pyramid_floats(B * H * W, D, C, levels), dtype=torch.float32, device=vol.device)
+        cpyr = torch.empty(geo_pyramid_floats(B * H * W, W2, 1, levels), dtype=torch.float32, device=vol.device)
+        _call("stx_geo_pyramid_fwd", _p(vol), _p(gpyr), B, D, H, W, C, levels)
+        _call("stx_geo_corr_fwd", _p(f1), _p(f2), _p(cpyr), B, Cf, H, W, W2, levels)
+        ctx.save_for_backward(f1, f2)
+        ctx.cfg = (B, D, H, W, C, Cf, W2, levels)
+        ctx.grads = grads
+        return gpyr, cpyr
+
+    @staticmethod
+    def backward(ctx, ggp, gcp):
+        f1, f2 = ctx.saved_tensors
+        B, D, H, W, C, Cf, W2, levels = ctx.cfg
+        if ctx.grads is not None:
+            ctx.grads.release()
+        gvol = gf1 = gf2 = None
+        if ggp is not None and ctx.needs_input_grad[0]:
+            gvol = torch.empty(B, D, H, W, C, dtype=torch.float32, device=f1.device)
+            _call("stx_geo_pyramid_bwd", _p(ggp.contiguous()), _p(gvol), B, D, H, W, C, levels)
+        if gcp is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            gf1 = torch.empty_like(f1) if ctx.needs_input_grad[1] else None
+            gf2 = torch.empty_like(f2) if ctx.needs_input_grad[2] else None
+            _call("stx_geo_corr_bwd", _p(gcp.contiguous()), _p(f1), _p(f2), _p(gf1), _p(gf2), B, Cf, H, W, W2, levels)
+        return gvol, gf1, gf2, None, None
+
+
+@fp32_region
+def geo_pyramids(vol, fmap1, fmap2, levels, grads=None):
+    """vol: dense [B, D, H, W, C] geometry volume; fmap1 [B, Cf, H, W], fmap2 [B, Cf, H, W2] -> (gpyr, cpyr)."""
+    f1, f2 = channel_major(fmap1), channel_major(fmap2)
+    _chk(vol, "geo_volume", 5)
+    _chk(f1, "init_fmap1", 4)
+    _chk(f2, "init_fmap2", 4)
+    B, D, H, W, C = vol.shape
+    if f1.shape[0] != B or f1.shape[2:] != (H, W) or f2.shape[:3] != f1.shape[:3]:
+        raise StxError(f"geometry encoding: volume {tuple(vol.shape)} (B, D, H, W, C) and feature maps {tuple(f1.shape)} / "
+                       f"{tuple(f2.shape)} do not match")
+    if C % 4:
+        raise StxError(f"geometry encoding: the volume's channel count ({C}) must be a multiple of 4")
+    if torch.is_grad_enabled() and (vol.requires_grad or f1.requires_grad or f2.requires_grad):
+        return GeoPyramidFn.apply(vol, f1, f2, levels, grads)
+    return GeoPyramidFn.forward(_NoCtx(), vol, f1, f2, levels, None)
+
+
+class GeoCorrFn(torch.autograd.Function):
+    """Combined_Geo_Encoding_Volume.corr (geometry.py:62-70): [B, H, W1, 1, W2] all-pairs row correlation."""
+
+    @staticmethod
+    def forward(ctx, f1, f2):
+        B, C, H, W1 = f1.shape
+        W2 = f2.shape[3]
+        corr = torch.empty(B, H, W1, 1, W2, dtype=torch.float32, device=f1.device)
+        _call("stx_geo_corr_fwd", _p(f1), _p(f2), _p(corr), B, C, H, W1, W2, 1)
+        ctx.save_for_backward(f1, f2)
+        return corr
+
+    @staticmethod
+    def backward(ctx, g):
+        f1, f2 = ctx.saved_tensors
+        B, C, H, W1 = f1.shape
+        gf1 = torch.empty_like(f1) if ctx.needs_input_grad[0] else None
+        gf2 = torch.empty_like(f2) if ctx.needs_input_grad[1] else None
+        _call("stx_geo_corr_bwd", _p(g.contiguous()), _p(f1), _p(f2), _p(gf1), _p(gf2), B, C, H, W1, f2.shape[3], 1)
+        return gf1, gf2
+
+
+@fp32_region
+def geo_corr(fmap1, fmap2):
+    f1, f2 = channel_major(fmap1), channel_major(fmap2)
+    _chk(f1, "fmap1", 4)
+    _chk(f2, "fmap2", 4)
+    if f1.shape[:3] != f2.shape[:3]:
+        raise StxError(f"corr: feature maps {tuple(f1.shape)} / {tuple(f2.shape)} do not match")
+    if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad):
+        return GeoCorrFn.apply(f1, f2)
+    return GeoCorrFn.forward(_NoCtx(), f1, f2)
+
+
+class GeoLookupFn(torch.autograd.Function):
+    """One call of Combined_Geo_Encoding_Volume (geometry.py:35-59) on stx_geo_lookup_fwd / _bwd.  cfg = (B, H, W, D, C, W2,
+    levels, radius).  Gradients go to the two pyramids only, accumulated through `grads` (_PyramidGrads)."""
+
+    @staticmethod
+    def forward(ctx, gpyr, cpyr, disp, coords, cfg, grads):
+        B, H, W, D, C, W2, levels, radius = cfg
+        out = torch.empty(B, levels * (C + 1) * (2 * radius + 1), H, W, dtype=torch.float32, device=disp.device)
+        _call("stx_geo_lookup_fwd", _p(gpyr), _p(cpyr), _p(disp), _p(coords), _p(out), *cfg)
+        ctx.save_for_backward(disp, coords)
+        ctx.cfg, ctx.grads, ctx.sizes = cfg, grads, (gpyr.numel(), cpyr.numel())
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        disp, coords = ctx.saved_tensors
+        first, (ggp, gcp) = ctx.grads.take(*ctx.sizes, disp.device)
+        _call("stx_geo_lookup_bwd", _p(gout.contiguous()), _p(disp), _p(coords), _p(ggp), _p(gcp), *ctx.cfg)
+        if first:
+            return ggp, gcp, None, None, None, None
+        return None, None, None, None, None, None
+
+
+@fp32_region
+def geo_lookup(gpyr, cpyr, disp, coords, cfg, grads):
+    """[B, levels * (C + 1) * (2 radius + 1), H, W]; disp [B, 1, H, W], coords: B * H * W values (the pixel's column)."""
+    B, H, W = cfg[:3]
+    if torch.is_grad_enabled() and (disp.requires_grad or coords.requires_grad):
+        raise StxError("Combined_Geo_Encoding_Volume: `disp` / `coords` must not require grad -- the lookup is differentiated "
+                       "with respect to the volumes only, as in the reference, which detaches disp before every call "
+                       "(igev_stereo.py:238); pass disp.detach()")
+    if disp.numel() != B * H * W or coords.numel() != B * H * W:
+        raise StxError(f"Combined_Geo_Encoding_Volume: disp {tuple(disp.shape)} / coords {tuple(coords.shape)} do not match the "
+                       f"volume's {B} x {H} x {W} pixels")
+    disp, coords = disp.detach().contiguous(), coords.detach().contiguous()
+    _chk(disp, "disp")
+    _chk(coords, "coords")
+    if torch.is_grad_enabled() and (gpyr.requires_grad or cpyr.requires_grad):
+        return GeoLookupFn.apply(gpyr, cpyr, disp, coords, cfg, grads)
+    return GeoLookupFn.forward(_NoCtx(), gpyr, cpyr, disp, coords, cfg, None)
+
+
+class ContextUpsampleFn(torch.autograd.Function):
+    """context_upsample (IGEVStereo/submodule.py:243-255) on stx_context_upsample_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, disp_low, up_weights):
+        B, _, h, w = disp_low.shape
+        out = torch.empty(B, 4 * h, 4 * w, dtype=torch.float32, device=disp_low.device)
+        _call("stx_context_upsample_fwd", _p(disp_low), _p(up_weights), _p(out), B, h, w)
+        ctx.save_for_backward(disp_low, up_weights)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        disp_low, up_weights = ctx.saved_tensors
+        B, _, h, w = disp_low.shape
+        gd = torch.empty_like(disp_low) if ctx.needs_input_grad[0] else None
+        gw = torch.empty_like(up_weights) if ctx.needs_input_grad[1] else None
+        _call("stx_context_upsample_bwd", _p(g.contiguous()), _p(disp_low), _p(up_weights), _p(gd), _p(gw), B, h, w)
+        return gd, gw
+
+
+@fp32_region
+def context_upsample(disp_low, up_weights):
+    """disp_low [B, 1, h, w], up_weights [B, 9, 4h, 4w] -> [B, 4h, 4w]."""
+    disp_low, up_weights = disp_low.contiguous(), up_weights.contiguous()
+    _chk(disp_low, "disp_low", 4)
+    _chk(up_weights, "up_weights", 4)
+    B, c, h, w = disp_low.shape
+    if c != 1 or up_weights.shape != (B, 9, 4 * h, 4 * w):
+        raise StxError(f"context_upsample: disp_low {tuple(disp_low.shape)} wants up_weights [B, 9, 4h, 4w], got "
+                       f"{tuple(up_weights.shape)}")
+    if torch.is_grad_enabled() and (disp_low.requires_grad or up_weights.requires_grad):
+        return ContextUpsampleFn.apply(disp_low, up_weights)
+    return ContextUpsampleFn.forward(_NoCtx(), disp_low, up_weights)
