@@ -12,7 +12,8 @@ pyramids are stored pixel-major in one buffer each (one pixel's whole search win
 launches (the all-pairs correlation runs on the matrix cores and writes its pooled levels in the same pass), and one lookup is
 ONE launch instead of about twenty ATen operators with volume-sized temporaries.  The lookup is differentiated with respect to
 `geo_volume`, `init_fmap1` and `init_fmap2`; its backward adds into per-pixel rows without atomics (bitwise reproducible), and
-all lookups of one backward pass accumulate into one gradient buffer per pyramid (ops._PyramidGrads).  `disp` and `coords`
+all lookups of one backward pass accumulate into one gradient buffer per pyramid (ops._PyramidGrads), which reaches the
+public `geo_volume_pyramid` / `init_corr_pyramid` tensors complete, so they may have other consumers.  `disp` and `coords`
 carry no gradient -- the reference detaches `disp` before every call (igev_stereo.py:238) -- and a tensor that requires
 grad is refused rather than silently given a zero gradient.
 """
@@ -38,13 +39,14 @@ class Combined_Geo_Encoding_Volume:
         if not vol.is_contiguous():
             vol = vol.contiguous()
         self._grads = ops._PyramidGrads()
-        self.geo_volume_pyramid, self.init_corr_pyramid = ops.geo_pyramids(vol, init_fmap1, init_fmap2, self.num_levels,
-                                                                          self._grads)
+        self.geo_volume_pyramid, self.init_corr_pyramid = ops.geo_pyramids(vol, init_fmap1, init_fmap2, self.num_levels)
+        # what the lookups read: aliases of the two public tensors that nothing else consumes (ops._PyramidGrads)
+        self._lookup_pyramids = ops.geo_lookup_pyramids(self.geo_volume_pyramid, self.init_corr_pyramid, self._grads)
         self._cfg = (b, h, w, d, c, init_fmap2.shape[3], self.num_levels, self.radius)
 
     @ops.fp32_region
     def __call__(self, disp, coords):
-        return ops.geo_lookup(self.geo_volume_pyramid, self.init_corr_pyramid, disp, coords, self._cfg, self._grads)
+        return ops.geo_lookup(*self._lookup_pyramids, disp, coords, self._cfg, self._grads)
 
     @staticmethod
     def corr(fmap1, fmap2):

@@ -1598,8 +1598,14 @@ def geo_pyramid_floats(rows, length, channels, levels):
 class _PyramidGrads:
     """The gradient buffers of the two pyramids of one `Combined_Geo_Encoding_Volume`, shared by all of its lookups within
     one backward pass: stx_geo_lookup_bwd ADDS into the rows a pixel owns, so the 22-32 lookups of a training step
-    accumulate in place and the pyramid-build node receives ONE gradient per pyramid (the lookup that runs first hands the
-    buffers to autograd, the others return nothing) instead of one dense pyramid-sized tensor per iteration."""
+    accumulate in place instead of handing autograd one dense pyramid-sized tensor per iteration.  The hand-off: the lookups
+    do not read the pyramid tensors the build node returns (the public `geo_volume_pyramid` / `init_corr_pyramid`) but
+    aliases of them behind an identity node (GeoPyramidHubFn) that nothing else can consume.  The lookup that runs first
+    returns the buffers to that node, the others add into them and return nothing; the engine runs the identity node only
+    after every lookup of the pass has run, and it alone passes the finished buffers on to the build node and drops them
+    here.  Any other consumer of the public pyramid tensors therefore meets ONE complete gradient per pyramid at the build
+    node and is summed with it in autograd's ordinary way.  Keyed by the autograd graph-task id: a second backward pass
+    (retained graph) starts from zeros."""
 
     def __init__(self):
         self.task, self.bufs = None, None
@@ -1623,7 +1629,7 @@ class GeoPyramidFn(torch.autograd.Function):
     geometry volume; vol dense [B, D, H, W, C], fmaps NCHW -> (gpyr, cpyr) flat buffers."""
 
     @staticmethod
-    def forward(ctx, vol, f1, f2, levels, grads):
+    def forward(ctx, vol, f1, f2, levels):
         B, D, H, W, C = vol.shape
         Cf, W2 = f1.shape[1], f2.shape[3]
         gpyr = torch.empty(geo_pyramid_floats(B * H * W, D, C, levels), dtype=torch.float32, device=vol.device)
@@ -1632,15 +1638,12 @@ class GeoPyramidFn(torch.autograd.Function):
         _call("stx_geo_corr_fwd", _p(f1), _p(f2), _p(cpyr), B, Cf, H, W, W2, levels)
         ctx.save_for_backward(f1, f2)
         ctx.cfg = (B, D, H, W, C, Cf, W2, levels)
-        ctx.grads = grads
         return gpyr, cpyr
 
     @staticmethod
     def backward(ctx, ggp, gcp):
         f1, f2 = ctx.saved_tensors
         B, D, H, W, C, Cf, W2, levels = ctx.cfg
-        if ctx.grads is not None:
-            ctx.grads.release()
         gvol = gf1 = gf2 = None
         if ggp is not None and ctx.needs_input_grad[0]:
             gvol = torch.empty(B, D, H, W, C, dtype=torch.float32, device=f1.device)
@@ -1649,11 +1652,35 @@ class GeoPyramidFn(torch.autograd.Function):
             gf1 = torch.empty_like(f1) if ctx.needs_input_grad[1] else None
             gf2 = torch.empty_like(f2) if ctx.needs_input_grad[2] else None
             _call("stx_geo_corr_bwd", _p(gcp.contiguous()), _p(f1), _p(f2), _p(gf1), _p(gf2), B, Cf, H, W, W2, levels)
-        return gvol, gf1, gf2, None, None
+        return gvol, gf1, gf2, None
+
+
+class GeoPyramidHubFn(torch.autograd.Function):
+    """Identity on the two pyramids, between the build node and the lookups of one object (see _PyramidGrads): the outputs
+    alias the inputs (no copy, no launch) and are read by the lookups only, so this node receives the shared gradient
+    buffers alone and hands them on once every lookup of the backward pass has added its part."""
+
+    @staticmethod
+    def forward(ctx, gpyr, cpyr, grads):
+        ctx.grads = grads
+        return gpyr.view_as(gpyr), cpyr.view_as(cpyr)
+
+    @staticmethod
+    def backward(ctx, ggp, gcp):
+        ctx.grads.release()
+        return ggp, gcp, None
+
+
+def geo_lookup_pyramids(gpyr, cpyr, grads):
+    """The pyramid tensors the lookups of one object read: (gpyr, cpyr) themselves where no graph is recorded, their aliases
+    behind GeoPyramidHubFn otherwise."""
+    if torch.is_grad_enabled() and (gpyr.requires_grad or cpyr.requires_grad):
+        return GeoPyramidHubFn.apply(gpyr, cpyr, grads)
+    return gpyr, cpyr
 
 
 @fp32_region
-def geo_pyramids(vol, fmap1, fmap2, levels, grads=None):
+def geo_pyramids(vol, fmap1, fmap2, levels):
     """vol: dense [B, D, H, W, C] geometry volume; fmap1 [B, Cf, H, W], fmap2 [B, Cf, H, W2] -> (gpyr, cpyr)."""
     f1, f2 = channel_major(fmap1), channel_major(fmap2)
     _chk(vol, "geo_volume", 5)
@@ -1666,8 +1693,8 @@ def geo_pyramids(vol, fmap1, fmap2, levels, grads=None):
     if C % 4:
         raise StxError(f"geometry encoding: the volume's channel count ({C}) must be a multiple of 4")
     if torch.is_grad_enabled() and (vol.requires_grad or f1.requires_grad or f2.requires_grad):
-        return GeoPyramidFn.apply(vol, f1, f2, levels, grads)
-    return GeoPyramidFn.forward(_NoCtx(), vol, f1, f2, levels, None)
+        return GeoPyramidFn.apply(vol, f1, f2, levels)
+    return GeoPyramidFn.forward(_NoCtx(), vol, f1, f2, levels)
 
 
 class GeoCorrFn(torch.autograd.Function):

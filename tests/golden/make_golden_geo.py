@@ -11,6 +11,11 @@ fp64: geometry.py:41 builds `dx` with torch.linspace's default dtype and :59 end
 generator makes both keep the dtype of their surroundings (a float64 linspace, an identity `Tensor.float`) around the calls --
 the reference file itself is untouched.
 Stored per tensor: the fp32 result, the fp64 result and d_ref = max|fp32 - fp64|: tests/golden/geo_lookup.npz.
+
+The second table of geo_config.py (SHAPE_CASES, the 22-call iteration pattern, the extra-consumer case, the larger upsampling
+cases; tests/test_geo_lookup_shapes.py) goes through the same reference classes, but whole tensors at those sizes do not belong
+in git: tests/golden/geo_lookup_shapes.npz keeps per tensor d_ref (`:dref`), max|fp64| (`:max`) and geo_config.subsample of the
+fp64 result (`:sub`).  Half a minute on eight cores, the 144x240 case included.
 """
 import contextlib
 import importlib.util
@@ -25,7 +30,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
-from tests.golden.geo_config import CASES, UPSAMPLE_CASES, inputs, upsample_inputs  # noqa: E402
+from tests.golden.geo_config import (CASES, EXTRA_CALLS, ITER_CASE, SHAPE_CASES, SHAPE_UPSAMPLE_CASES, UPSAMPLE_CASES,  # noqa: E402
+                                     inputs, iter_inputs, shape_inputs, shape_upsample_inputs, subsample, upsample_inputs)
 
 
 def reference():
@@ -53,9 +59,9 @@ def keep_fp64():
         torch.linspace, torch.Tensor.float = linspace, to_float
 
 
-def run_lookup(Ref, tag, dtype):
-    B, C, D, H, W, W2, Cf, L, r = CASES[tag]
-    geo, f1, f2, coords, disps, gws = inputs(tag)
+def run_lookup(Ref, tag, dtype, shapes=False):
+    B, C, D, H, W, W2, Cf, L, r = (SHAPE_CASES if shapes else CASES)[tag]
+    geo, f1, f2, coords, disps, gws = (shape_inputs if shapes else inputs)(tag)
     geo, f1, f2 = (t.to(dtype).requires_grad_() for t in (geo, f1, f2))
     ctx = keep_fp64() if dtype == torch.float64 else contextlib.nullcontext()
     with ctx:
@@ -68,8 +74,27 @@ def run_lookup(Ref, tag, dtype):
     return {"out_a": outs[0], "out_b": outs[1], "corr": corr, "g_geo": geo.grad, "g_fmap1": f1.grad, "g_fmap2": f2.grad}
 
 
-def run_upsample(ref_up, tag, dtype):
-    disp, wts, gw = upsample_inputs(tag)
+def run_iterations(Ref, dtype, calls, extra):
+    """`calls` lookups on one object, losses summed; extra: plus a weighted sum of every level of both pyramids (the object's
+    public attributes, [b*h*w, C, 1, D_i] and [b*h*w, 1, 1, W2_i] in the reference)."""
+    B, C, D, H, W, W2, Cf, L, r = ITER_CASE
+    geo, f1, f2, coords, disps, gws, wg, wc = iter_inputs()
+    geo, f1, f2 = (t.to(dtype).requires_grad_() for t in (geo, f1, f2))
+    with keep_fp64() if dtype == torch.float64 else contextlib.nullcontext():
+        fn = Ref(f1, f2, geo, num_levels=L, radius=r)
+        outs = [fn(d.to(dtype), coords.to(dtype)) for d in disps[:calls]]
+    assert all(o.dtype == dtype for o in outs)
+    loss = sum((o * g.to(dtype)).sum() for o, g in zip(outs, gws))
+    if extra:
+        for i in range(L):
+            loss = loss + (fn.geo_volume_pyramid[i].reshape(B, H, W, C, D >> i) * wg[i].to(dtype)).sum()
+            loss = loss + (fn.init_corr_pyramid[i].reshape(B, H, W, W2 >> i) * wc[i].to(dtype)).sum()
+    loss.backward()
+    return {"outs": torch.stack(outs), "g_geo": geo.grad, "g_fmap1": f1.grad, "g_fmap2": f2.grad}
+
+
+def run_upsample(ref_up, tag, dtype, shapes=False):
+    disp, wts, gw = (shape_upsample_inputs if shapes else upsample_inputs)(tag)
     disp, wts = disp.to(dtype).requires_grad_(), wts.to(dtype).requires_grad_()
     out = ref_up(disp, wts)
     assert out.dtype == dtype
@@ -91,6 +116,26 @@ def main():
             store[f"{tag}:{k}:dref"] = np.float64((a.double() - b).abs().max().item())
             print(f"{tag:12s} {k:13s} {tuple(a.shape)}  max|ref| {b.abs().max().item():.4g}  d_ref {store[f'{tag}:{k}:dref']:.3e}")
     path = os.path.join(HERE, "geo_lookup.npz")
+    np.savez_compressed(path, **store)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    main_shapes(Ref, ref_up)
+
+
+def main_shapes(Ref, ref_up):
+    store = {}
+    jobs = [(tag, lambda dt, t=tag: run_lookup(Ref, t, dt, shapes=True)) for tag in SHAPE_CASES]
+    jobs += [("iter22", lambda dt: run_iterations(Ref, dt, None, False)), ("extra", lambda dt: run_iterations(Ref, dt, EXTRA_CALLS, True))]
+    jobs += [("up_" + tag, lambda dt, t=tag: run_upsample(ref_up, t, dt, shapes=True)) for tag in SHAPE_UPSAMPLE_CASES]
+    for tag, fn in jobs:
+        r32, r64 = fn(torch.float32), fn(torch.float64)
+        for k in r32:
+            a, b = r32[k].detach(), r64[k].detach()
+            assert a.dtype == torch.float32 and b.dtype == torch.float64
+            store[f"{tag}:{k}:dref"] = np.float64((a.double() - b).abs().max().item())
+            store[f"{tag}:{k}:max"] = np.float64(b.abs().max().item())
+            store[f"{tag}:{k}:sub"] = subsample(b).numpy().copy()
+            print(f"{tag:16s} {k:13s} {tuple(a.shape)}  max|ref| {b.abs().max().item():.4g}  d_ref {store[f'{tag}:{k}:dref']:.3e}", flush=True)
+    path = os.path.join(HERE, "geo_lookup_shapes.npz")
     np.savez_compressed(path, **store)
     print("wrote", path, os.path.getsize(path), "bytes")
 
