@@ -478,21 +478,6 @@ __global__ __launch_bounds__(ACV_THREADS) void scale_channels_kernel(const float
 
 constexpr int ACV_WGRAD_BLOCKS = 1024;
 
-// Dynamic LDS above 64 KiB needs the kernel's MaxDynamicSharedMemorySize attribute raised.  Asked once per kernel and size
-// (not on every launch); a refusal -- a device or partition mode with less LDS than gfx950's 160 KiB -- makes the caller take
-// the cache-fed kernel instead of failing.
-bool acv_lds_granted(const void* kern, size_t lds, int& granted) {
-    if (lds <= 64 * 1024 || (int)lds <= granted) return true;
-    if (granted < 0) return false;                                   // refused before
-    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        granted = -1;
-        return false;
-    }
-    granted = (int)lds;
-    return true;
-}
-
 int acv_grid(size_t n) {
     size_t g = (n + ACV_THREADS - 1) / ACV_THREADS;
     return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
@@ -513,7 +498,7 @@ extern "C" int stx_dwconv_hw_fwd(const float* x, const float* w, const int* dil,
         const int TW = 2 * (int)vpb, EW = TW + 2 * DWR_HALO;
         const size_t lds = (size_t)DWR_RING * EW * C * sizeof(float);
         const int nf4 = EW * (C / 4);
-        if (stx_tune(STX_TUNE_DWCONV_ROLL) && lds <= 160 * 1024 && nf4 <= 4 * ACV_THREADS && H >= 8) {
+        if (stx_tune(STX_TUNE_DWCONV_ROLL) && nf4 <= 4 * ACV_THREADS && H >= 8) {
             const int nstrips = stx_cdiv(W, TW);
             const long long base = (long long)B * D * nstrips;
             int nseg = (int)((768 + base - 1) / base);
@@ -521,8 +506,8 @@ extern "C" int stx_dwconv_hw_fwd(const float* x, const float* w, const int* dil,
             if (nseg > H / 8) nseg = H / 8 > 0 ? H / 8 : 1;          // a segment re-stages 6 halo rows: keep it >= 8 rows
             const int seg_rows = stx_cdiv(H, nseg);
             nseg = stx_cdiv(H, seg_rows);
-            static int granted = 0;
-            if (base * nseg < (1ll << 31) && acv_lds_granted((const void*)dwconv_hw_roll_kernel, lds, granted)) {
+            // (a refusal -- a device or partition mode with less LDS than gfx950's 160 KiB -- takes the cache-fed kernel)
+            if (base * nseg < (1ll << 31) && stx_lds_try((const void*)dwconv_hw_roll_kernel, lds)) {
                 hipLaunchKernelGGL(dwconv_hw_roll_kernel, dim3((unsigned)(base * nseg)), dim3(ACV_THREADS), lds, (hipStream_t)stream, a,
                                    TW, nstrips, nseg, seg_rows);
                 return stx_check_launch("dwconv_hw_fwd(roll)");
@@ -553,9 +538,8 @@ extern "C" int stx_dwconv_hw_wgrad(const float* x, const float* gy, const int* d
         const long long base = (long long)B * D * nstrips;
         // (base > ACV_WGRAD_BLOCKS -- more (plane, strip) items than partial rows of the workspace, e.g. B >= 5 at 576x960 -- takes
         //  the cache-fed kernel below: about twice the time per launch, profiles/r05_dwconv_rolling_window_ab_callU.txt)
-        static int granted = 0;
-        if (stx_tune(STX_TUNE_DWCONV_ROLL) && lds <= 160 * 1024 && EW * (C / 4) <= 4 * ACV_THREADS && H >= 8 && base <= ACV_WGRAD_BLOCKS &&
-            acv_lds_granted((const void*)dwconv_hw_wgrad_roll_kernel, lds, granted)) {
+        if (stx_tune(STX_TUNE_DWCONV_ROLL) && EW * (C / 4) <= 4 * ACV_THREADS && H >= 8 && base <= ACV_WGRAD_BLOCKS &&
+            stx_lds_try((const void*)dwconv_hw_wgrad_roll_kernel, lds)) {
             int nseg = (int)(ACV_WGRAD_BLOCKS / base);
             if (nseg > H / 8) nseg = H / 8;
             if (nseg < 1) nseg = 1;
@@ -594,9 +578,7 @@ extern "C" int stx_ac_volume_bwd(const float* gvol, const float* Lc, const float
                 "ac_volume_bwd: bad args");
     const size_t lds = (size_t)D * W * 4;
     STX_REQUIRE(lds <= 150 * 1024, "ac_volume_bwd: D * W = %d x %d does not fit the LDS image (use the three-kernel form)", D, W);
-    if (hipFuncSetAttribute((const void*)ac_volume_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return stx_set_error(STX_ERR_LAUNCH, "ac_volume_bwd: %d bytes of dynamic LDS refused by this device (the library is "
-                                             "built for the 160 KiB LDS of gfx950)", (int)lds);
+    if (int rc = stx_lds_require((const void*)ac_volume_bwd_kernel, lds, "ac_volume_bwd")) return rc;
     hipLaunchKernelGGL(ac_volume_bwd_kernel, dim3((unsigned)(B * H)), dim3(ACV_THREADS), lds, (hipStream_t)stream, gvol, Lc, Rc, prob,
                        gL, gR, gprob, Cc, H, W, D, mask_left);
     return stx_check_launch("ac_volume_bwd");

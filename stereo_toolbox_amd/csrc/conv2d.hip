@@ -22,7 +22,6 @@
 // Optional epilogue: per-channel sum / sum of squares of the raw output for train-mode BatchNorm (one row per workgroup;
 // with `groups` views in the batch the grid is split so that no workgroup's run crosses a view: per-view statistics).
 #include "stx_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -316,21 +315,18 @@ extern "C" int stx_conv2d_fwd(const float* x, const float* w, float* out, float*
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.nHt = stx_cdiv(H, C2_TH); a.nWt = stx_cdiv(W, C2_TW); a.groups = groups;
     const int grid = conv2d_grid(groups);
-    static const int pad = getenv("STX_C2_PAD") ? atoi(getenv("STX_C2_PAD")) : 8;            // (profiling only: 4, 8 or 12)
+    int pad = stx_tune(STX_TUNE_C2_PAD);                                                      // (profiling only: 4, 8 or 12)
+    if (pad != 4 && pad != 12) pad = 8;
     const size_t lds = ((size_t)9 * Cin * 16 + (size_t)2 * 192 * (Cin + pad) + (size_t)2 * Cout) * 4;   // (192: SLOT of the kernel)
     void (*k)(Conv2dArgs) = Cin == 64 ? conv2d_march_kernel<4> : conv2d_march_kernel<2>;
     if (pad == 4) k = Cin == 64 ? conv2d_march_kernel<4, 0, 4> : conv2d_march_kernel<2, 0, 4>;
     if (pad == 12) k = Cin == 64 ? conv2d_march_kernel<4, 0, 12> : conv2d_march_kernel<2, 0, 12>;
-    static const int abl = getenv("STX_C2_ABLATE") ? atoi(getenv("STX_C2_ABLATE")) : 0;      // (profiling only)
-    if (abl && Cin == 64 && pad == 8) {
+    const int abl = stx_tune(STX_TUNE_C2_ABLATE);                                             // (profiling only)
+    if (abl && Cin == 64 && pad == 8)
         k = abl == 1 ? conv2d_march_kernel<4, 1> : abl == 2 ? conv2d_march_kernel<4, 2> : abl == 3 ? conv2d_march_kernel<4, 3>
           : abl == 4 ? conv2d_march_kernel<4, 4> : abl == 7 ? conv2d_march_kernel<4, 7> : abl == 8 ? conv2d_march_kernel<4, 8>
           : conv2d_march_kernel<4, 15>;
-        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    }
-    // (set on every launch, like the 3-D kernels: the attribute belongs to the current device's copy of the function)
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)) != hipSuccess)
-        return stx_set_error(STX_ERR_LAUNCH, "conv2d_fwd: %zu B of LDS refused", lds);
+    if (int rc = stx_lds_require((const void*)k, lds, "conv2d_fwd")) return rc;
     hipLaunchKernelGGL(k, dim3(grid), dim3(C2_THREADS), lds, (hipStream_t)stream, a);
     return stx_check_launch("conv2d_fwd");
 }

@@ -1347,18 +1347,17 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3d_wgrad_reduce4_kernel(cons
     }
 }
 
-template <typename K>
-int launch_with_lds(K kernel, dim3 grid, size_t lds, hipStream_t st, ConvArgs a) {
-    if (lds > 160 * 1024) return stx_set_error(STX_ERR_ARG, "conv3d: LDS tile of %zu B exceeds 160 KiB", lds);
-    if (lds > 64 * 1024)
-        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// Launch of every forward kernel of this file (CONV_THREADS lanes): the LDS tile granted first.
+template <typename K, typename... Args>
+int launch_with_lds(K kernel, dim3 grid, size_t lds, hipStream_t st, Args... args) {
+    if (int rc = stx_lds_require((const void*)kernel, lds, "conv3d")) return rc;
     static const bool report = getenv("STX_REPORT_OCCUPANCY") != nullptr;    // (diagnostic: resident workgroups per CU)
     if (report) {
         int nb = -1;
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kernel, CONV_THREADS, lds);
         fprintf(stderr, "[stx] conv3d launch: grid %u x %u, %zu B LDS, %d workgroups per CU\n", grid.x, grid.y, lds, nb);
     }
-    hipLaunchKernelGGL(kernel, grid, dim3(CONV_THREADS), lds, st, a);
+    hipLaunchKernelGGL(kernel, grid, dim3(CONV_THREADS), lds, st, args...);
     return 0;
 }
 
@@ -1373,14 +1372,23 @@ size_t conv_lds_bytes(int CK, int NT) {
     return t > red ? t : red;
 }
 
-// Persistent pipelined launch: 256 * (workgroups per CU the LDS tile admits, at most 2) workgroups share the tiles evenly.
-template <typename K>
-int launch_persistent(K kernel, size_t lds, hipStream_t st, ConvArgs a, int ntiles, int grid) {
-    if (lds > 160 * 1024) return stx_set_error(STX_ERR_ARG, "conv3d: LDS tile of %zu B exceeds 160 KiB", lds);
-    if (lds > 64 * 1024)
-        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CONV_THREADS), lds, st, a, ntiles);
-    return 0;
+// Persistent pipelined kernel (128 output channels) with its wave grid WN = 1, 2 or 4.
+template <int S>
+void (*pgemm_kernel(int wn))(ConvArgs, int) {
+    return wn == 4 ? conv3d_pgemm_kernel<3, S, CONV_TD, CONV_TH, 4, 8, 4>
+         : wn == 2 ? conv3d_pgemm_kernel<3, S, CONV_TD, CONV_TH, 4, 8, 2> : conv3d_pgemm_kernel<3, S, CONV_TD, CONV_TH, 4, 8>;
+}
+
+// March kernel for STX_MARCH_BS and an epilogue: 0 plain, 1 general, 2 partial sums added, 3 residual, 4 raw, 5 raw on whole tiles.
+void (*march_kernel(int bs, int epi))(MarchArgs) {
+    switch (epi) {
+    case 0: return bs ? conv3d_marchw_kernel<1, 0> : conv3d_marchw_kernel<0, 0>;
+    case 2: return bs ? conv3d_marchw_kernel<1, 2> : conv3d_marchw_kernel<0, 2>;
+    case 3: return bs ? conv3d_marchw_kernel<1, 3> : conv3d_marchw_kernel<0, 3>;
+    case 4: return bs ? conv3d_marchw_kernel<1, 4> : conv3d_marchw_kernel<0, 4>;
+    case 5: return bs ? conv3d_marchw_kernel<1, 5> : conv3d_marchw_kernel<0, 5>;
+    default: return bs ? conv3d_marchw_kernel<1, 1> : conv3d_marchw_kernel<0, 1>;
+    }
 }
 
 // Implicit-GEMM kernel for NT column blocks of 32 output channels and K chunks of CK input channels.
@@ -1451,7 +1459,7 @@ extern "C" int stx_deconv3d_fwd_blocks(int Di, int Hi, int Wi) {
 // that owns outputs): the single source for the launch below and for stx_conv3d_fwd_stat_rows.
 struct ConvPlan { int kind; int march_wgs; int pgrid; long long rows; };     // kind: 0 march, 1 pipelined (128 channels), 2 implicit GEMM
 static int persistent_grid(size_t lds, long long ntiles) {
-    int per_cu = (int)((160 * 1024) / (lds + 512));
+    int per_cu = (int)(STX_LDS_MAX / (lds + 512));
     per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
     const long long g = 256ll * per_cu;
     return (int)(g > ntiles ? ntiles : g);
@@ -1525,20 +1533,7 @@ extern "C" int stx_conv3d_fwd(const float* x, const float* wp, float* out, const
             // output (GPU call F of round 3, 32 -> 32 L0: 0.757 -> 0.767 ms).  STX_MARCH_EPI: 1 = straight-line epilogue for
             // the launches that admit it, 0 = general epilogue always.
             const int bs = stx_tune(STX_TUNE_MARCH_BS), epi_fast = stx_tune(STX_TUNE_MARCH_EPI);
-            void (*mk_gen)(MarchArgs) = bs ? conv3d_marchw_kernel<1, 1> : conv3d_marchw_kernel<0, 1>;
-            void (*mk_plain)(MarchArgs) = bs ? conv3d_marchw_kernel<1, 0> : conv3d_marchw_kernel<0, 0>;
-            void (*mk_acc)(MarchArgs) = bs ? conv3d_marchw_kernel<1, 2> : conv3d_marchw_kernel<0, 2>;
-            void (*mk_res)(MarchArgs) = bs ? conv3d_marchw_kernel<1, 3> : conv3d_marchw_kernel<0, 3>;
-            void (*mk_raw)(MarchArgs) = bs ? conv3d_marchw_kernel<1, 4> : conv3d_marchw_kernel<0, 4>;
-            void (*mk_rawf)(MarchArgs) = bs ? conv3d_marchw_kernel<1, 5> : conv3d_marchw_kernel<0, 5>;
-            hipFuncSetAttribute((const void*)mk_rawf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
             const bool whole = a.Ho % MW2_TH == 0 && a.Wo % MW2_MW == 0;
-            hipFuncSetAttribute((const void*)mk_raw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            hipFuncSetAttribute((const void*)mk_res, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            hipFuncSetAttribute((const void*)mk_plain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            hipFuncSetAttribute((const void*)mk_acc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            void (*mk)(MarchArgs) = mk_gen;
-            hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
             m2.xs = Cin; m2.os = Cout; m2.wq_total = Cin / 8; m2.wnt_total = conv_nt(Cout);
             const int nk = Cin / 32, nn = stx_cdiv(Cout, 32);
             for (int ns = 0; ns < nn; ++ns)
@@ -1553,9 +1548,8 @@ extern "C" int stx_conv3d_fwd(const float* x, const float* wp, float* out, const
                     // (the straight-line epilogues read the partial sums through the OUTPUT descriptor: acc_in is `out`)
                     const bool plain = epi_fast && !(m.c.residual && m.acc_in) && m.c.relu < 2;
                     const bool raw = !m.acc_in && !m.c.residual && !m.c.scale && !m.c.bias && m.c.relu == 0;
-                    hipLaunchKernelGGL(plain ? (raw ? (whole && m.ncout == 32 ? mk_rawf : mk_raw) : m.acc_in ? mk_acc
-                                                        : (m.c.residual ? mk_res : mk_plain)) : mk,
-                                       dim3(nb2), dim3(256), lds2, st, m);
+                    const int epi = plain ? (raw ? (whole && m.ncout == 32 ? 5 : 4) : m.acc_in ? 2 : (m.c.residual ? 3 : 0)) : 1;
+                    if (int rc = launch_with_lds(march_kernel(bs, epi), dim3(nb2), lds2, st, m)) return rc;
                 }
             return stx_check_launch("conv3d_fwd(march)");
         }
@@ -1577,15 +1571,7 @@ extern "C" int stx_conv3d_fwd(const float* x, const float* wp, float* out, const
             // (STX_CONV_WN: 2 = the default, only the 64-channel kernels change their wave grid; 3 / 4 = this kernel as two rows x two
             //  blocks / four rows x one block per wave: 0.242 / 0.239 vs 0.235 ms on 128->128 L2 -- no gain, kept as switches)
             const int wn = stx_tune(STX_TUNE_CONV_WN) == 4 ? 4 : (stx_tune(STX_TUNE_CONV_WN) == 3 ? 2 : 1);
-            if (wn >= 4)
-                rc = stride == 1 ? launch_persistent(conv3d_pgemm_kernel<3, 1, CONV_TD, CONV_TH, 4, 8, 4>, lds, st, a, (int)nt_all, plan.pgrid)
-                                 : launch_persistent(conv3d_pgemm_kernel<3, 2, CONV_TD, CONV_TH, 4, 8, 4>, lds, st, a, (int)nt_all, plan.pgrid);
-            else if (wn >= 2)
-                rc = stride == 1 ? launch_persistent(conv3d_pgemm_kernel<3, 1, CONV_TD, CONV_TH, 4, 8, 2>, lds, st, a, (int)nt_all, plan.pgrid)
-                                 : launch_persistent(conv3d_pgemm_kernel<3, 2, CONV_TD, CONV_TH, 4, 8, 2>, lds, st, a, (int)nt_all, plan.pgrid);
-            else
-            rc = stride == 1 ? launch_persistent(conv3d_pgemm_kernel<3, 1, CONV_TD, CONV_TH, 4, 8>, lds, st, a, (int)nt_all, plan.pgrid)
-                             : launch_persistent(conv3d_pgemm_kernel<3, 2, CONV_TD, CONV_TH, 4, 8>, lds, st, a, (int)nt_all, plan.pgrid);
+            rc = launch_with_lds(stride == 1 ? pgemm_kernel<1>(wn) : pgemm_kernel<2>(wn), dim3(plan.pgrid), lds, st, a, (int)nt_all);
             if (rc) return rc;
             return stx_check_launch("conv3d_fwd(pipelined)");
         }
@@ -1735,7 +1721,7 @@ extern "C" int stx_conv3d_wgrad(const float* f, const float* c, float* dw, float
     {                                                                                                             \
         const size_t lds = (LDS_);                                                                                \
         void (*wk)(WgradArgs) = conv3d_wgrad_kernel<KS_, S_, TH_, TW_, NW_, PIPE_>;                               \
-        hipFuncSetAttribute((const void*)wk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
+        if (int rc = stx_lds_require((const void*)wk, lds, "conv3d_wgrad")) return rc;                            \
         hipLaunchKernelGGL(wk, grid, dim3(NW_ * 64), lds, st, a);                                                 \
     }
     if (ks == 3 && stride == 1) {

@@ -530,7 +530,7 @@ extern "C" int stx_conv3d_c1_fwd(const float* x, const float* w, const float* re
         long long g = C1F_WGS;
         if (g > units / 4) g = units / 4 > 0 ? units / 4 : 1;
         const size_t lds = (size_t)2 * C1F_NV * 27 * 4;
-        hipFuncSetAttribute((const void*)conv_c1_fwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (int rc = stx_lds_require((const void*)conv_c1_fwd_mfma_kernel, lds, "conv3d_c1_fwd(mfma)")) return rc;
         hipLaunchKernelGGL(conv_c1_fwd_mfma_kernel, dim3((unsigned)g), dim3(C1_THREADS), lds, (hipStream_t)stream, x, w,
                            residual, out, B, D, H, W, nHt, nWt, (int)ncols);
         return stx_check_launch("conv3d_c1_fwd(mfma)");
@@ -540,7 +540,7 @@ extern "C" int stx_conv3d_c1_fwd(const float* x, const float* w, const float* re
     a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin;
     a.nDt = stx_cdiv(D, C1_TD); a.nHt = stx_cdiv(H, C1_TH); a.nWt = stx_cdiv(W, C1_TW);
     a.ntiles = B * a.nDt * a.nHt * a.nWt;
-    hipFuncSetAttribute((const void*)conv_c1_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_TILE_BYTES);
+    if (int rc = stx_lds_require((const void*)conv_c1_fwd_kernel, C1_TILE_BYTES, "conv3d_c1_fwd")) return rc;
     hipLaunchKernelGGL(conv_c1_fwd_kernel, dim3(a.ntiles), dim3(C1_THREADS), C1_TILE_BYTES, (hipStream_t)stream, a);
     return stx_check_launch("conv3d_c1_fwd");
 }
@@ -578,10 +578,9 @@ extern "C" int stx_conv3d_c1_wgrad(const float* x, const float* gy, float* dw, f
     const int nblk = a.ntiles < C1_WGRAD_BLOCKS ? a.ntiles : C1_WGRAD_BLOCKS;
     const size_t lds = C1_TILE_BYTES + 256 * 4;
     hipStream_t st = (hipStream_t)stream;
-    hipFuncSetAttribute((const void*)conv_c1_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (int rc = stx_lds_require((const void*)conv_c1_wgrad_kernel, lds, "conv3d_c1_wgrad")) return rc;
     hipLaunchKernelGGL(conv_c1_wgrad_kernel, dim3(nblk), dim3(C1_THREADS), lds, st, a);
-    int rc = stx_check_launch("conv3d_c1_wgrad");
-    if (rc) return rc;
+    if (int rc = stx_check_launch("conv3d_c1_wgrad")) return rc;
     hipLaunchKernelGGL(c1_colsum_kernel, dim3(Cin * 27), dim3(C1_THREADS), 0, st, workspace, nblk, Cin * 27, dw);
     return stx_check_launch("conv3d_c1_colsum");
 }

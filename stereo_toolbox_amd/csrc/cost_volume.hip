@@ -387,10 +387,10 @@ extern "C" int stx_cost_volume_fwd(const float* Lg, const float* Rg, int Cg, int
         lds = 0;
         if (G) lds += (size_t)(CV_WT + NR) * (Cg + 4) * 4;
         if (Cc) lds += (size_t)(CV_WT + NR) * (Cc + 4) * 4;
-        if (lds <= 160 * 1024 || DC == 1) break;
+        if (lds <= STX_LDS_MAX || DC == 1) break;
         DC = (DC + 1) / 2;
     }
-    STX_REQUIRE(lds <= 160 * 1024 && DC <= CV_MAX_DC, "cost_volume_fwd: feature tile (%zu B) exceeds LDS", lds);
+    STX_REQUIRE(lds <= STX_LDS_MAX && DC <= CV_MAX_DC, "cost_volume_fwd: feature tile (%zu B) exceeds LDS", lds);
     dim3 grid(stx_cdiv(W, CV_WT) * stx_cdiv(D, DC) * B * H);
     hipStream_t st = (hipStream_t)stream;
     // reciprocals for e / ncols by multiply-high (exact while e < 2^16: the largest tile has Cg*NR elements)
@@ -400,9 +400,7 @@ extern "C" int stx_cost_volume_fwd(const float* Lg, const float* Rg, int Cg, int
     const int ablate = 0;
 #define CV_LAUNCH(CPG_)                                                                                       \
     {                                                                                                         \
-        if (lds > 64 * 1024)                                                                                  \
-            hipFuncSetAttribute((const void*)cost_volume_fwd_kernel<CPG_>,                                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
+        if (int rc = stx_lds_require((const void*)cost_volume_fwd_kernel<CPG_>, lds, "cost_volume_fwd")) return rc; \
         hipLaunchKernelGGL(cost_volume_fwd_kernel<CPG_>, grid, dim3(CVF_THREADS), lds, st, Lg, Rg, Cg, G, Lc, \
                            Rc, Cc, scale, vol, H, W, D, DC, mask_left, magicL, magicR, ablate);               \
     }

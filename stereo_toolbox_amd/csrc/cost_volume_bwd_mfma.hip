@@ -460,7 +460,7 @@ __global__ __launch_bounds__((CVB2_NCW + CVB2_NLW) * 64) void cost_volume_bwd_mf
 template <int CPG, int QPW, int NS, int GT, int CCT>
 int cvb_launch(const CvbArgs& a, size_t lds, hipStream_t st) {
     auto kern = cost_volume_bwd_mfma_kernel<CPG, QPW, NS, GT, CCT>;
-    if (lds > 64 * 1024) hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (int rc = stx_lds_require((const void*)kern, lds, "cost_volume_bwd(mfma)")) return rc;
     int grid = 256;
     if (stx_tune(STX_TUNE_CVB_GRID) > 0) grid = stx_tune(STX_TUNE_CVB_GRID);           // tests: force short / long runs
     if (grid > a.macros) grid = a.macros;
@@ -498,7 +498,7 @@ int stx_cv_bwd_mfma(const float* gvol, const float* Lg, const float* Rg, int Cg,
     a.nteams = 8;
     a.team = (team_env && 2 * a.nt > 16 && 2 * a.nt <= 32 && nch == 6 && B * H >= a.nteams && stx_tune(STX_TUNE_CVB_GRID) <= 0) ? 1 : 0;
     const size_t lds = ((size_t)2 * (CVB2_DC * cvb_pitch(G) + G) + (size_t)CVB2_RING * (Cg + 4)) * 4;
-    if (lds > 160 * 1024) return -1;
+    if (lds > STX_LDS_MAX) return -1;
     hipStream_t st = (hipStream_t)stream;
     const int GQ = G / 4;
     // GwcNet / ACVNet volumes (320 channels in 40 groups, 12 or 0 concat channels): constants folded, STX_CVB_NSET chunks

@@ -451,9 +451,7 @@ constexpr int CVM_PF_DEFAULT = 1;      // one tile ahead.  STX_CV_PF = 2 selects
 template <int CPG, int QPW, int NCW, int NSW, int ND, bool SCALE = false, int PF = 1>
 int cvm_launch(const CvmArgs& a, int wgs_per_cu, size_t lds, hipStream_t st) {
     auto kern = cost_volume_fwd_mfma_kernel<CPG, QPW, NCW, NSW, ND, SCALE, PF>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return stx_set_error(STX_ERR_LAUNCH, "cost_volume_fwd: %d bytes of dynamic LDS refused by this device", (int)lds);
+    if (int rc = stx_lds_require((const void*)kern, lds, "cost_volume_fwd(mfma)")) return rc;
     int grid = 256 * wgs_per_cu;
     if (stx_tune(STX_TUNE_CV_GRID) > 0) grid = stx_tune(STX_TUNE_CV_GRID);            // tests: force multi-unit runs
     if (grid > a.macros) grid = a.macros;
@@ -478,7 +476,7 @@ int stx_cv_fwd_mfma(const float* Lg, const float* Rg, int Cg, int G, const float
     if (nd > 6) return -1;
     const int VS = G + 4, DS = CVM_T * VS + 4, CS = cvm_cs(Cc), TC = CVM_T * (nd + 2);
     size_t lds = 2 * ((size_t)(G ? CVM_T * DS : 0) + (size_t)(Cc ? TC * CS : 0)) * 4;      // double-buffered image + tables
-    if (lds > 160 * 1024) return -1;
+    if (lds > STX_LDS_MAX) return -1;
     CvmArgs a;
     a.Lg = Lg; a.Rg = Rg; a.Lc = Lc; a.Rc = Rc; a.scale = scale; a.vol = vol;
     a.B = B; a.H = H; a.W = W; a.D = D; a.G = G; a.Cc = Cc; a.mask_left = mask_left;
@@ -500,9 +498,9 @@ int stx_cv_fwd_mfma(const float* Lg, const float* Rg, int Cg, int G, const float
     // PF = 2 keeps one tile per compute wave in an LDS slot (2 KiB per quad and 4 channels of a group): taken when it fits beside the images
     const int ncw = GQ <= 4 ? 4 : (GQ <= 10 ? 10 : 8), qpw = GQ <= 10 ? 1 : 2;
     const size_t slots = (size_t)ncw * qpw * 8 * (cpg / 4) * 64 * 4;
-    if (pf == 2 && GQ > 0 && lds + slots <= 160 * 1024) lds += slots; else pf = 1;
+    if (pf == 2 && GQ > 0 && lds + slots <= STX_LDS_MAX) lds += slots; else pf = 1;
     // workgroups per CU: what the LDS images admit, at most 2; the wave layouts below are sized for <= 16 waves per workgroup
-    int wgs = (int)((160 * 1024) / (lds + 1024));
+    int wgs = (int)(STX_LDS_MAX / (lds + 1024));
     wgs = wgs < 1 ? 1 : (wgs > 2 ? 2 : wgs);
     hipStream_t st = (hipStream_t)stream;
     // wave layouts <channels per group, quads per compute wave, compute waves, store waves, ring bound> (measured in round 2:

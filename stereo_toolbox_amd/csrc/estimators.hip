@@ -291,16 +291,9 @@ static int modal_launch(const float* x, float* out, float* aux, int B, int D, in
     if (D <= ES_LDS_MAX_D) {
         const dim3 grid(stx_cdiv(HW, ES_WAVE), B);
         const size_t lds = (size_t)D * ES_WAVE * sizeof(float);
-        if (kind == 0) {
-            if (lds > 64 * 1024)
-                hipFuncSetAttribute((const void*)unimodal_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(unimodal_lds_kernel, grid, dim3(ES_WAVE), lds, st, x, out, aux, D, HW);
-        } else {
-            if (lds > 64 * 1024)
-                hipFuncSetAttribute((const void*)dominant_modal_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds);
-            hipLaunchKernelGGL(dominant_modal_lds_kernel, grid, dim3(ES_WAVE), lds, st, x, out, aux, D, HW);
-        }
+        const auto kern = kind == 0 ? unimodal_lds_kernel : dominant_modal_lds_kernel;
+        if (int rc = stx_lds_require((const void*)kern, lds, what)) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(ES_WAVE), lds, st, x, out, aux, D, HW);
     } else {
         const dim3 grid(stx_cdiv(HW, ES_THREADS), B);
         if (kind == 0) hipLaunchKernelGGL(unimodal_kernel, grid, dim3(ES_THREADS), 0, st, x, out, aux, D, HW);
@@ -344,9 +337,7 @@ extern "C" int stx_split_mode(const float* x, float* mode, unsigned char* mask, 
     hipStream_t st = (hipStream_t)stream;
     if (D <= ES_LDS_MAX_D) {
         const size_t lds = (size_t)D * ES_WAVE * sizeof(float);
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute((const void*)split_mode_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return stx_set_error(STX_ERR_LAUNCH, "split_mode: %d bytes of dynamic LDS refused by this device", (int)lds);
+        if (int rc = stx_lds_require((const void*)split_mode_lds_kernel, lds, "split_mode")) return rc;
         hipLaunchKernelGGL(split_mode_lds_kernel, dim3(stx_cdiv(HW, ES_WAVE), B), dim3(ES_WAVE), lds, st, x, mode, mask, D, HW);
     } else {
         hipLaunchKernelGGL(split_mode_kernel, dim3(stx_cdiv(HW, ES_THREADS), B), dim3(ES_THREADS), 0, st, x, mode, mask, D, HW);

@@ -41,7 +41,7 @@ constexpr int GL_THREADS = 128;       // lookup kernels: lanes (pixels) per work
 constexpr int GL_MAX_LEVELS = 3;
 constexpr int GL_MAX_RADIUS = 8;
 constexpr int GP_THREADS = 256;       // pyramid build
-constexpr int GP_LDS_BYTES = 64 * 1024;
+constexpr size_t GP_LDS_BYTES = STX_LDS_DEFAULT;   // (no grant needed)
 constexpr int GC_THREADS = 256;       // correlation: four waves
 constexpr int CU_THREADS = 256;
 
@@ -411,9 +411,9 @@ int geo_pyramid_launch(const float* vol_in, float* vol_out, const float* pyr_in,
     GeoShape s;
     if (int rc = geo_shape(s, B, H, W, D, C, 1 << (GL_MAX_LEVELS - 1), levels, 1, what)) return rc;
     int WT = 16;
-    while (WT > 1 && (size_t)D * (WT * C + C) * sizeof(float) > (size_t)GP_LDS_BYTES) WT >>= 1;
+    while (WT > 1 && (size_t)D * (WT * C + C) * sizeof(float) > GP_LDS_BYTES) WT >>= 1;
     const size_t lds = (size_t)D * (WT * C + C) * sizeof(float);
-    STX_REQUIRE(lds <= (size_t)GP_LDS_BYTES, "%s: D * C = %d does not fit the LDS tile", what, D * C);
+    STX_REQUIRE(lds <= GP_LDS_BYTES, "%s: D * C = %d does not fit the LDS tile", what, D * C);
     hipLaunchKernelGGL(geo_pyramid_kernel, dim3(stx_cdiv(W, WT), H, B), dim3(GP_THREADS), lds, (hipStream_t)stream, vol_in, vol_out,
                        pyr_in, pyr_out, s, WT);
     return stx_check_launch(what);

@@ -473,8 +473,7 @@ static int head_fwd_launch(const float* cost, float* disp, float* stats, int B, 
     dim3 grid(stx_cdiv(W, HD_THREADS), H, B);
     const size_t lds = hd_lds_bytes(Dc, D);
     if (hd_use_lds(lds)) {
-        if (lds > 64 * 1024)
-            hipFuncSetAttribute((const void*)head_fwd_lds_kernel<AC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (int rc = stx_lds_require((const void*)head_fwd_lds_kernel<AC>, lds, "head_fwd")) return rc;
         hipLaunchKernelGGL(head_fwd_lds_kernel<AC>, grid, dim3(HD_THREADS), lds, (hipStream_t)stream, cost, disp, stats,
                            Dc, Hc, Wc, D, H, W);
     } else {

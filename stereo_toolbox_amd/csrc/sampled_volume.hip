@@ -292,7 +292,7 @@ extern "C" int stx_sampled_volume_fwd(const float* Lg, const float* Rg, int Cg, 
     a.B = B; a.H = H; a.W = W; a.S = S; a.G = G; a.cpg = G ? Cg / G : 0; a.Cc = Cc; a.CT = G + 2 * Cc + 1; a.CTp = CTp;
     if (int rc = sv_check(a, "sampled_volume_fwd")) return rc;
     const size_t lds = (size_t)SV_TW * (CTp + 1) * 4;
-    STX_REQUIRE(lds <= 64 * 1024, "sampled_volume_fwd: %d channels exceed the LDS tile", CTp);
+    STX_REQUIRE(lds <= STX_LDS_DEFAULT, "sampled_volume_fwd: %d channels exceed the LDS tile", CTp);
     STX_REQUIRE(Cc <= 16, "sampled_volume_fwd: %d concat channels exceed the kernel's register tile (16)", Cc);
     const dim3 grid(stx_cdiv(W, SV_TW), H, B * stx_cdiv(S, SV_SPB));
     hipStream_t st = (hipStream_t)stream;
@@ -321,7 +321,7 @@ extern "C" int stx_sampled_volume_bwd(const float* gvol, const float* Lg, const 
     STX_REQUIRE(G <= 4 * SV_MAXGPW && Cc <= 16, "sampled_volume_bwd: G = %d / Cc = %d exceed the kernel's register tiles", G, Cc);
     STX_REQUIRE(G == 0 || a.cpg == 4 || a.cpg == 8, "sampled_volume_bwd: %d channels per group unsupported (4 or 8)", a.cpg);
     const size_t lds_tile = (size_t)SV_TW * (CTp + 1) * 4;
-    STX_REQUIRE(lds_tile <= 64 * 1024, "sampled_volume_bwd: %d channels exceed the LDS tile", CTp);
+    STX_REQUIRE(lds_tile <= STX_LDS_DEFAULT, "sampled_volume_bwd: %d channels exceed the LDS tile", CTp);
     hipStream_t st = (hipStream_t)stream;
     const size_t HW = (size_t)H * W;
     if (G && hipMemsetAsync(gRg, 0, (size_t)B * Cg * HW * 4, st) != hipSuccess) return stx_set_error(STX_ERR_LAUNCH, "sampled_volume_bwd: memset");
@@ -333,19 +333,17 @@ extern "C" int stx_sampled_volume_bwd(const float* gvol, const float* Lg, const 
     if (!stx_tune(STX_TUNE_SV_BWD_V1))
         for (int n = 1; n <= 4 && !nsplit; n *= 2) {
             const size_t win = ((size_t)stx_cdiv(G, n) * cpg + Cc) * SV_XW * 4;
-            if (lds_tile + win <= (n < 4 ? 80 : 160) * 1024 && (long long)B * n <= 65535) nsplit = n;
+            if (lds_tile + win <= (n < 4 ? STX_LDS_MAX / 2 : STX_LDS_MAX) && (long long)B * n <= 65535) nsplit = n;
         }
     const bool priv = nsplit > 0;
     a.nsplit = priv ? nsplit : 1;
     const size_t lds = lds_tile + (priv ? ((size_t)stx_cdiv(G, a.nsplit) * cpg + Cc) * SV_XW * 4 : 0);
     dim3 grid(stx_cdiv(W, SV_TW), H, B * a.nsplit);
     const bool small = stx_cdiv(G, a.nsplit) <= 20;               // <= 5 groups per wave: half the accumulator registers
-#define SV_BWD(CPG_, PRIV_, GPW_)                                                                                \
-    {                                                                                                            \
-        if (lds > 64 * 1024)                                                                                     \
-            hipFuncSetAttribute((const void*)sampled_volume_bwd_kernel<CPG_, PRIV_, GPW_>,                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-        hipLaunchKernelGGL((sampled_volume_bwd_kernel<CPG_, PRIV_, GPW_>), grid, dim3(SV_THREADS), lds, st, a);  \
+#define SV_BWD(CPG_, PRIV_, GPW_)                                                                                      \
+    {                                                                                                                  \
+        if (int rc = stx_lds_require((const void*)sampled_volume_bwd_kernel<CPG_, PRIV_, GPW_>, lds, "sampled_volume_bwd")) return rc; \
+        hipLaunchKernelGGL((sampled_volume_bwd_kernel<CPG_, PRIV_, GPW_>), grid, dim3(SV_THREADS), lds, st, a);        \
     }
     if (a.cpg == 8) {
         if (priv && small) SV_BWD(8, true, 5) else if (priv) SV_BWD(8, true, 10) else SV_BWD(8, false, 10)

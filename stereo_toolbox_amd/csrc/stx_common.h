@@ -150,9 +150,18 @@ static inline void stx_begin() { (void)hipGetLastError(); }
 
 static inline int stx_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Dynamic LDS of one workgroup: up to STX_LDS_DEFAULT a kernel launches as it is, up to STX_LDS_MAX (the CU's whole LDS)
+// only after the device has granted it.  A launcher with a fallback kernel asks with stx_lds_try (false = refused, no error
+// left behind); one without returns what stx_lds_require returns.  Both ask on every call and keep no state: the grant
+// belongs to the current device's copy of the kernel.
+constexpr size_t STX_LDS_DEFAULT = 64 * 1024;
+constexpr size_t STX_LDS_MAX = 160 * 1024;
+bool stx_lds_try(const void* kern, size_t bytes);
+int stx_lds_require(const void* kern, size_t bytes, const char* what);
+
 // Tuning / A-B switches of the library.  Each has a default (the measured-best path), is read from its environment
 // variable ONCE, when the library is loaded, and can be changed at run time through the C-ABI (stx_set_tuning: tests and
-// tools/kernel_bench.py flip them inside one process).  None changes results beyond fp32 rounding.
+// tools/kernel_bench.py flip them inside one process).  None but the *_ABLATE switches changes results beyond fp32 rounding.
 enum StxTune {
     STX_TUNE_MARCH_BS,       // STX_MARCH_BS       1  march kernel: one accumulator per (output, input plane), summed in the epilogue
     STX_TUNE_MARCH_EPI,      // STX_MARCH_EPI      1  march kernel: straight-line epilogue for launches without partial sums / residual / Mish
@@ -174,6 +183,8 @@ enum StxTune {
     STX_TUNE_CVB_NSET,       // STX_CVB_NSET       3  cost volume backward: chunks in flight per loader lane (2..4)
     STX_TUNE_SV_BWD_V1,      // STX_SV_BWD_V1      0  CFNet cascade-volume backward: global atomics only
     STX_TUNE_DWCONV_ROLL,    // STX_DWCONV_ROLL    1  ACVNet patch convolutions: rolling window of input rows in LDS (0 = the cache-fed kernel of rounds 3-4)
+    STX_TUNE_C2_PAD,         // STX_C2_PAD         8  2-D 3x3 convolution: LDS row padding in floats, 4 / 8 / 12 (anything else: 8)
+    STX_TUNE_C2_ABLATE,      // STX_C2_ABLATE      0  profiling, Cin 64 at the default pad: bit mask of the kernel stages left out (conv2d.hip, ABL)
     STX_TUNE_COUNT
 };
 int stx_tune(StxTune id);

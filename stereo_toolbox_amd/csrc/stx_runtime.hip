@@ -19,6 +19,20 @@ int stx_check_launch(const char* what) {
     return STX_OK;
 }
 
+bool stx_lds_try(const void* kern, size_t bytes) {
+    if (bytes <= STX_LDS_DEFAULT) return true;
+    if (bytes > STX_LDS_MAX) return false;
+    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+int stx_lds_require(const void* kern, size_t bytes, const char* what) {
+    if (bytes > STX_LDS_MAX) return stx_set_error(STX_ERR_ARG, "%s: %zu B of LDS exceed the %zu B of a CU", what, bytes, STX_LDS_MAX);
+    if (!stx_lds_try(kern, bytes)) return stx_set_error(STX_ERR_LAUNCH, "%s: %zu B of LDS refused by this device", what, bytes);
+    return STX_OK;
+}
+
 extern "C" const char* stx_last_error(void) { return g_err; }
 
 extern "C" const char* stx_build_info(void) {
@@ -37,7 +51,7 @@ struct TuneEntry { const char* name; int value; };
 TuneEntry g_tune[STX_TUNE_COUNT] = {
     {"STX_MARCH_BS", 1}, {"STX_MARCH_EPI", 1}, {"STX_MARCH_ABLATE", 0}, {"STX_WGRAD_ABLATE", 0}, {"STX_WGRAD_MARCH", 3}, {"STX_WGRAD_GRID", 0}, {"STX_CONV_L1_MARCH", 0}, {"STX_CONV_S2_DENSE", 1}, {"STX_CONV_WN", 2},
     {"STX_CV_OLD", 0}, {"STX_CV_GRID", 0}, {"STX_CV_PF", 0}, {"STX_CV_UNITS", 1}, {"STX_CV_WIN", 0}, {"STX_CVB_OLD", 0}, {"STX_CVB_TEAM", 0}, {"STX_CVB_GRID", 0}, {"STX_CVB_NSET", 3},
-    {"STX_SV_BWD_V1", 0}, {"STX_DWCONV_ROLL", 1},
+    {"STX_SV_BWD_V1", 0}, {"STX_DWCONV_ROLL", 1}, {"STX_C2_PAD", 8}, {"STX_C2_ABLATE", 0},
 };
 struct TuneInit {                       // environment read once, when the library is loaded
     TuneInit() {

@@ -568,8 +568,7 @@ int stx_wgrad_march_launch(const float* x, const float* gy, float* slab, int B, 
     a.nsteps = ncols * D;
     const int npairs = (CF / 32) * (CC / 32);
     void (*kern)(WmArgs) = bn ? conv3d_wgrad_march_kernel<true> : conv3d_wgrad_march_kernel<false>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WM_LDS_BYTES) != hipSuccess)
-        return stx_set_error(STX_ERR_LAUNCH, "conv3d_wgrad(march): %d bytes of dynamic LDS refused by this device", (int)WM_LDS_BYTES);
+    if (int rc = stx_lds_require((const void*)kern, WM_LDS_BYTES, "conv3d_wgrad(march)")) return rc;
     hipLaunchKernelGGL(kern, dim3(nchunks, npairs), dim3(WM_THR), WM_LDS_BYTES, (hipStream_t)stream, a);
     return stx_check_launch("conv3d_wgrad(march)");
 }
@@ -587,9 +586,7 @@ int stx_wgrad_march_s2_launch(const float* f, const float* c, float* slab, int B
     a.ncols = (int)ncols;
     a.nsteps = ncols * Dc;
     const int npairs = (CF / 32) * (CC / 32);
-    if (hipFuncSetAttribute((const void*)conv3d_wgrad_march_s2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)W2_LDS_BYTES) != hipSuccess)
-        return stx_set_error(STX_ERR_LAUNCH, "conv3d_wgrad(march s2): %d bytes of dynamic LDS refused by this device", (int)W2_LDS_BYTES);
+    if (int rc = stx_lds_require((const void*)conv3d_wgrad_march_s2_kernel, W2_LDS_BYTES, "conv3d_wgrad(march s2)")) return rc;
     hipLaunchKernelGGL(conv3d_wgrad_march_s2_kernel, dim3(nchunks, npairs), dim3(WM_THR), W2_LDS_BYTES, (hipStream_t)stream, a,
                        Df, Hf, Wf, stx_tune(STX_TUNE_WGRAD_ABLATE));     // (profiling switch: 1 no staging loads, 2 no MFMA groups, 3 no LDS writes)
     return stx_check_launch("conv3d_wgrad(march s2)");

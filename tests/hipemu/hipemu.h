@@ -53,7 +53,14 @@ typedef int hipError_t;
 static inline hipError_t hipGetLastError() { return 0; }
 static inline const char* hipGetErrorString(hipError_t) { return "hipemu"; }
 static inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }
-static inline hipError_t hipFuncSetAttribute(const void*, int, int) { return 0; }
+// (refuses more than hipemu_set_lds_limit(bytes) allows -- hipemu_impl.cpp; negative = no limit, the default.  Since the last
+//  hipemu_set_lds_limit: hipemu_lds_refusals counts the refused grants, hipemu_max_launch_lds is the largest dynamic LDS launched)
+extern "C" int hipemu_lds_limit, hipemu_lds_refusals, hipemu_max_launch_lds;
+static inline hipError_t hipFuncSetAttribute(const void*, int, int value) {
+    const bool refused = hipemu_lds_limit >= 0 && value > hipemu_lds_limit;
+    hipemu_lds_refusals += refused;
+    return refused;
+}
 static inline hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* n, const void*, int, size_t) { *n = 1; return 0; }
 #define hipFuncAttributeMaxDynamicSharedMemorySize 8
 
@@ -345,5 +352,6 @@ inline void run_grid(dim3 grid, dim3 block, size_t shmem, F body) {
 
 template <typename K, typename... Args>
 inline void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, size_t shmem, hipStream_t, Args... args) {
+    if ((long long)shmem > hipemu_max_launch_lds) hipemu_max_launch_lds = (int)shmem;
     hipemu::run_grid(grid, block, shmem, [=]() { kernel(args...); });
 }

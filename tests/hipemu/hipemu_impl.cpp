@@ -20,3 +20,10 @@ __asm__(
     "    popq %rbp\n"
     "    ret\n"
     ".size hipemu_switch,.-hipemu_switch\n");
+
+// Largest dynamic-LDS grant the hipFuncSetAttribute stub allows (tests of the launchers' refusal paths); negative = no limit.
+// Setting it restarts the two records a test reads to see WHICH kernel a launcher took: grants refused, largest LDS launched.
+extern "C" {
+int hipemu_lds_limit = -1, hipemu_lds_refusals = 0, hipemu_max_launch_lds = 0;
+void hipemu_set_lds_limit(int bytes) { hipemu_lds_limit = bytes; hipemu_lds_refusals = 0; hipemu_max_launch_lds = 0; }
+}

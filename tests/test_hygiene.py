@@ -242,7 +242,7 @@ def test_emulator_kernel_suite_under_address_sanitizer():
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:detect_stack_use_after_return=0:use_sigaltstack=0")
     sel = ("test_cost_volume_fwd_bwd or test_conv3d_fwd or test_deconv3d_fwd or test_conv3d_wgrad or test_bn_train_fwd_bwd "
            "or test_head_fwd_bwd or test_conv3d_c1_fwd_wgrad or test_dwconv_hw_fwd_bwd or test_sampled_volume_fwd_bwd "
-           "or test_estimators or test_mish")
+           "or test_estimators or test_mish or test_conv2d_pad_clamp")
     r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_kernels.py", "-x", "-q", "-m", "not gpu", "-k", sel,
                         "-p", "no:cacheprovider"], cwd=root, env=env, capture_output=True, text=True)
     tail = (r.stdout + r.stderr)[-3000:]

@@ -1158,3 +1158,100 @@ def test_bn_groups_match_separate_calls(be, two, monkeypatch):
     _close(bg, outs[0][4] + outs[1][4], rtol=1e-6, atol=1e-6)
     for a, b in zip(rm + rv, rm2 + rv2):
         assert torch.equal(a.cpu(), b.cpu())
+
+
+# ------------------------------------------------------------------------------- dynamic-LDS grants (stx_lds_try / stx_lds_require)
+@pytest.fixture
+def emu_lds_limit():
+    """Setter of the largest dynamic-LDS grant the emulator's hipFuncSetAttribute allows (tests/hipemu/hipemu_impl.cpp; a real
+    device is never made to refuse); no limit again after the test."""
+    import ctypes
+    from tests.emu_util import emu_lib
+    set_limit = ctypes.CDLL(emu_lib().path).hipemu_set_lds_limit
+    yield set_limit
+    set_limit(-1)
+
+
+def test_dwconv_hw_takes_the_cache_fed_kernel_when_the_lds_grant_is_refused(emu_lds_limit):
+    """The rolling-window launchers have a fallback: with grants above 64 KiB refused (tile of this shape: 8 x 56 voxels x 40
+    channels x 4 B = 71 680 B) STX_DWCONV_ROLL = 1 gives what STX_DWCONV_ROLL = 0 gives, and no error.  That the cache-fed
+    kernel ran is read off the emulator's records: both launchers were refused, and nothing above 64 KiB was launched (without
+    the limit the same calls launch the 71 680 B tile)."""
+    import ctypes
+    from tests.backends import Backend
+    from tests.emu_util import emu_lib
+    be = Backend("emu")
+    emu = ctypes.CDLL(emu_lib().path)
+    refusals, max_lds = (ctypes.c_int.in_dll(emu, n) for n in ("hipemu_lds_refusals", "hipemu_max_launch_lds"))
+    B, C, D, H, W = 1, 40, 2, 19, 61
+    torch.manual_seed(21)
+    x, gy, wts = torch.randn(B, D, H, W, C), torch.randn(B, D, H, W, C), torch.randn(C, 9)
+    dd = torch.tensor([1 + (q * 3) // (C // 4) for q in range(C // 4)], dtype=torch.int32)
+    old = be.lib.get_tuning("STX_DWCONV_ROLL")
+    try:
+        res, seen = {}, {}
+        for roll, limit in ((1, -1), (1, 64 * 1024), (0, 64 * 1024)):
+            emu_lds_limit(limit)
+            be.lib.set_tuning("STX_DWCONV_ROLL", roll)
+            out = be.empty(B, D, H, W, C)
+            be.call("stx_dwconv_hw_fwd", ptr(x), ptr(wts), ptr(dd), ptr(out), B, D, H, W, C, 0)
+            ws = be.empty(be.raw("stx_dwconv_hw_wgrad_workspace_floats")(C))
+            gw = be.empty(C, 9)
+            be.call("stx_dwconv_hw_wgrad", ptr(x), ptr(gy), ptr(dd), ptr(gw), ptr(ws), B, D, H, W, C)
+            res[roll] = (out, gw)
+            seen[roll, limit] = (refusals.value, max_lds.value)
+    finally:
+        be.lib.set_tuning("STX_DWCONV_ROLL", old)
+    assert seen[1, -1] == (0, 71680), seen                                  # the measure sees the rolling-window kernel
+    assert seen[1, 64 * 1024][0] >= 2 and seen[1, 64 * 1024][1] <= 64 * 1024, seen
+    assert torch.equal(res[1][0], res[0][0])
+    _close(res[1][1], res[0][1], rtol=1e-5, atol=1e-4)
+
+
+def _conv2d_small(be):
+    """stx_conv2d_fwd at the smallest 64-input-channel shape of tests/test_conv2d.py; returns (run, reference, LDS bytes)."""
+    B, Ci, Co, H, W = 1, 64, 128, 16, 16
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn(B, Ci, H, W, generator=g)
+    w = torch.randn(Co, Ci, 3, 3, generator=g) * 0.1
+    xd, wd = be.dev(x.permute(0, 2, 3, 1).contiguous()), be.dev(w.permute(0, 2, 3, 1).contiguous())
+
+    def run():
+        out = be.empty(B, H, W, Co)
+        be.call("stx_conv2d_fwd", ptr(xd), ptr(wd), ptr(out), None, B, H, W, Ci, Co, 0, 1)
+        return out.cpu().permute(0, 3, 1, 2)
+    return run, F.conv2d(x, w, None, 1, 1), (9 * Ci * 16 + 2 * 192 * (Ci + 8) + 2 * Co) * 4
+
+
+def test_conv2d_reports_a_refused_lds_grant_and_keeps_no_state(emu_lds_limit):
+    """A launcher without a fallback returns the library's error, naming the call and the bytes it asked for; the same call
+    succeeds in the same process once the grant is given (nothing is cached)."""
+    import ctypes
+    from stereo_toolbox_amd._capi import StxError
+    from tests.backends import Backend
+    be = Backend("emu")
+    run, ref, lds = _conv2d_small(be)
+    last_error = ctypes.CDLL(be.lib.path).stx_last_error
+    last_error.restype = ctypes.c_char_p
+    emu_lds_limit(64 * 1024)
+    with pytest.raises(StxError):
+        run()
+    msg = last_error().decode()
+    assert "conv2d_fwd" in msg and str(lds) in msg, msg
+    emu_lds_limit(-1)
+    err = (run() - ref).abs().max().item()
+    assert err <= 2e-5 * ref.abs().max().item() + 1e-6, err
+
+
+def test_conv2d_pad_clamp(be, tune):
+    """STX_C2_PAD: the LDS row padding changes bank conflicts only, and a value outside {4, 8, 12} is the default 8 for the
+    kernel AND for the LDS size (the emulator's AddressSanitizer build runs this test too)."""
+    run, ref, _ = _conv2d_small(be)
+    outs = []
+    for v in (0, 4, 8, 12, 99):
+        tune("STX_C2_PAD", v)
+        outs.append(run())
+    for o in outs[1:]:
+        assert torch.equal(outs[0], o)
+    err = (outs[0] - ref).abs().max().item()
+    assert err <= 2e-5 * ref.abs().max().item() + 1e-6, err
