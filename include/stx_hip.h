@@ -363,6 +363,33 @@ int stx_context_upsample_fwd(const float* disp_low, const float* up_weights, flo
 int stx_context_upsample_bwd(const float* g, const float* disp_low, const float* up_weights, float* gdisp, float* gweights, int B,
                              int h, int w, void* stream);
 
+/* ---- corr1d.hip: all-pairs 1-D correlation pyramid and lookup of the RAFT family -----------------------------------------
+ * CorrBlock1D / CorrBlockFast1D / PytorchAlternateCorrBlock1D (models/RAFTStereo/corr.py:31-156, utils/utils.py:59-74; used
+ * unchanged by Selective-RAFT) and the disparity-indexed CorrBlock1D of DEFOM-Stereo (models/DEFOMStereo/corr.py:113-181).
+ * The PYRAMID is pixel-major like the correlation pyramid above: level i is [B*H*W1][W2 >> i], the levels one behind the other,
+ * stx_corr1d_pyramid_floats(B*H*W1, W2, levels) floats in all; levels 1..4, and the last level must keep at least 2 positions
+ * (the reference normalises by length - 1).
+ * stx_corr1d_pyramid_fwd: level 0 = scale * sum_c fmap1[b][c][h][w1] * fmap2[b][c][h][w2] on the matrix cores (the reference's
+ *   scale is 1 / sqrt(C)) AND the pooled levels, one launch; fmap1 [B][C][H][W1], fmap2 [B][C][H][W2], any C.
+ * stx_corr1d_pyramid_bwd: gcpyr (gradient of every level) -> gfmap1, gfmap2 (either may be NULL); every element written.
+ * The lookup: `jobs` is a HOST array of njobs x 4 floats (level, radius, alpha, mult), njobs 1..8, radius 1..8.  Per pixel p,
+ *   job j writes the 2 radius + 1 samples of p's row of its level at x = (base[p] - alpha * disp[p]) * mult + k, k = -radius ..
+ *   radius (linear interpolation, zero outside the row), to the channels after those of the jobs before it:
+ *   out [B][sum_j (2 radius_j + 1)][H][W1].  base, disp: [B*H*W1]; disp may be NULL (then alpha is not used).
+ *   RAFT: (i, r, 0, 2^-i), base = coords[:, 0].  DEFOM: (i, r, 1, 2^-i); scaling: (0, r_s, s, 1) per s of scale_list.
+ * _bwd: gout -> ADDED (+=) to gcpyr, which the caller clears before the first of the lookups whose gradients it wants
+ *   summed; a pixel touches only its own rows: no atomics, bitwise reproducible.  base and disp carry no gradient (the
+ *   reference detaches them: raft_stereo.py:154, defom_stereo.py:142). */
+long long stx_corr1d_pyramid_floats(long long rows, int W2, int levels);
+int stx_corr1d_pyramid_fwd(const float* fmap1, const float* fmap2, float* cpyr, int B, int C, int H, int W1, int W2, int levels,
+                           float scale, void* stream);
+int stx_corr1d_pyramid_bwd(const float* gcpyr, const float* fmap1, const float* fmap2, float* gfmap1, float* gfmap2, int B, int C,
+                           int H, int W1, int W2, int levels, float scale, void* stream);
+int stx_corr1d_lookup_fwd(const float* cpyr, const float* base, const float* disp, const float* jobs, int njobs, float* out, int B,
+                          int H, int W1, int W2, int levels, void* stream);
+int stx_corr1d_lookup_bwd(const float* gout, const float* base, const float* disp, const float* jobs, int njobs, float* gcpyr,
+                          int B, int H, int W1, int W2, int levels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

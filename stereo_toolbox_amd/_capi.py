@@ -102,6 +102,12 @@ SIGNATURES = {
     "stx_geo_lookup_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "stx_context_upsample_fwd": [_P, _P, _P, _I, _I, _I, _P],
     "stx_context_upsample_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    # corr1d.hip
+    "stx_corr1d_pyramid_floats": [_L, _I, _I],
+    "stx_corr1d_pyramid_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "stx_corr1d_pyramid_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "stx_corr1d_lookup_fwd": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    "stx_corr1d_lookup_bwd": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

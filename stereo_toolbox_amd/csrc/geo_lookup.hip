@@ -18,7 +18,8 @@
 // lookups of one training step accumulate into one gradient buffer per pyramid (ops.py GeoLookupFn).
 //
 // Kernels.
-//   geo_corr_fwd      one GEMM W1 x C x W2 per image row on v_mfma_f32_16x16x4_f32 (operands straight from the NCHW rows, one
+//   geo_corr_fwd      (the kernels of corr1d.hip at scale 1, corr_pyramid.h)
+//                     one GEMM W1 x C x W2 per image row on v_mfma_f32_16x16x4_f32 (operands straight from the NCHW rows, one
 //                     dword per lane, 64-byte segments); the pooled levels come out of the accumulators (neighbouring lanes
 //                     hold neighbouring w2) in the same launch.
 //   geo_corr_bwd      g_fmap1 = G . fmap2, g_fmap2 = G^T . fmap1 on the same instruction, G = the gradient of level 0 plus
@@ -33,7 +34,7 @@
 //   context_upsample  one lane per four output pixels (they share the low-resolution cell): 9 x float4 of weights, 9 taps.
 //                     Backward: the weights' gradient in the same shape; the disparity's gradient as a GATHER over the 9 x 16
 //                     output pixels a low-resolution pixel feeds (fixed order, no atomics).
-#include "stx_common.h"
+#include "corr_pyramid.h"
 
 namespace {
 
@@ -42,7 +43,6 @@ constexpr int GL_MAX_LEVELS = 3;
 constexpr int GL_MAX_RADIUS = 8;
 constexpr int GP_THREADS = 256;       // pyramid build
 constexpr size_t GP_LDS_BYTES = STX_LDS_DEFAULT;   // (no grant needed)
-constexpr int GC_THREADS = 256;       // correlation: four waves
 constexpr int CU_THREADS = 256;
 
 struct GeoShape {
@@ -51,27 +51,11 @@ struct GeoShape {
 };
 
 // ------------------------------------------------------------------------------------------------ pyramid addressing
-__device__ __host__ inline size_t geo_level_offset(long long rows, int len, int C, int lvl) {
-    size_t off = 0;
-    for (int j = 0; j < lvl; ++j) off += (size_t)rows * (size_t)(len >> j) * (size_t)C;
-    return off;
-}
-
-// position of the window's first tap: floor(x) - r as an integer that cannot overflow, and the fraction all 2r+1 samples share
-__device__ __forceinline__ int geo_window(float x, int radius, float& frac) {
-    const float xf = floorf(x);
-    frac = x - xf;
-    return (int)fminf(fmaxf(xf, -1.0e6f), 1.0e6f) - radius;
-}
-
+// (geo_level_offset, geo_window, geo_tap1, geo_lerp: corr_pyramid.h)
 __device__ __forceinline__ float4 geo_tap4(const float* row, int t, int len, int C) {
     if (t < 0 || t >= len) return make_float4(0.f, 0.f, 0.f, 0.f);
     return stx_ld4(row + (size_t)t * C);
 }
-
-__device__ __forceinline__ float geo_tap1(const float* row, int t, int len) { return (t < 0 || t >= len) ? 0.f : row[t]; }
-
-__device__ __forceinline__ float geo_lerp(float a, float b, float f) { return fmaf(f, b, (1.f - f) * a); }
 
 // ------------------------------------------------------------------------------------------------ lookup
 // grid: (cdiv(npix, GL_THREADS), levels * (C/4 + 1)); blockIdx.y = level * (C/4 + 1) + job, job < C/4: channel quad, else correlation
@@ -229,112 +213,6 @@ __global__ __launch_bounds__(GP_THREADS) void geo_pyramid_kernel(const float* __
     }
 }
 
-// ------------------------------------------------------------------------------------------------ all-pairs row correlation
-// grid (cdiv(W1, 16), H, B), four waves; a wave owns the w2 tiles 4 g .. 4 g + 3 of the groups g = wave, wave + 4, ...
-// MFMA 16x16x4 f32: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], D[row = 4 (l >> 4) + r][col = l & 15].
-__global__ __launch_bounds__(GC_THREADS) void geo_corr_fwd_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
-                                                                  float* __restrict__ cpyr, int B, int C, int H, int W1, int W2,
-                                                                  int levels) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int w1_0 = (int)blockIdx.x * 16, h = (int)blockIdx.y, b = (int)blockIdx.z;
-    const size_t HW1 = (size_t)H * W1, HW2 = (size_t)H * W2;
-    const float* a_row = f1 + (size_t)b * C * HW1 + (size_t)h * W1;
-    const float* b_row = f2 + (size_t)b * C * HW2 + (size_t)h * W2;
-    const size_t rows = (size_t)B * H * W1;
-    const int len1 = W2 >> 1, len2 = W2 >> 2;
-    float* l0 = cpyr;
-    float* l1 = cpyr + geo_level_offset((long long)rows, W2, 1, 1);
-    float* l2 = cpyr + geo_level_offset((long long)rows, W2, 1, 2);
-    const bool a_ok = w1_0 + li < W1;
-    for (int w2_0 = wave * 64; w2_0 < W2; w2_0 += 256) {
-        f32x4 acc[4];
-        for (int n = 0; n < 4; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int c0 = 0; c0 < C; c0 += 4) {
-            const int c = c0 + lk;
-            const bool c_ok = c < C;
-            const float a = (a_ok && c_ok) ? a_row[(size_t)c * HW1 + w1_0 + li] : 0.f;
-            float bv[4];
-            for (int n = 0; n < 4; ++n) {
-                const int w2 = w2_0 + 16 * n + li;
-                bv[n] = (c_ok && w2 < W2) ? b_row[(size_t)c * HW2 + w2] : 0.f;
-            }
-            for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv[n], acc[n], 0, 0, 0);
-        }
-        for (int n = 0; n < 4; ++n) {
-            const int w2 = w2_0 + 16 * n + li;
-            for (int r = 0; r < 4; ++r) {
-                const int w1 = w1_0 + 4 * lk + r;
-                const size_t row = ((size_t)b * H + h) * W1 + w1;
-                const float v0 = acc[n][r];
-                const float v1 = (v0 + __shfl_xor(v0, 1)) * 0.5f;          // avg_pool of lanes (w2, w2 + 1), w2 even
-                const float v2 = (v1 + __shfl_xor(v1, 2)) * 0.5f;          // ... of level-1 elements (w2/2, w2/2 + 1), w2 % 4 == 0
-                if (w1 < W1) {
-                    if (w2 < W2) l0[row * W2 + w2] = v0;
-                    if (levels > 1 && !(li & 1) && (w2 >> 1) < len1) l1[row * len1 + (w2 >> 1)] = v1;
-                    if (levels > 2 && !(li & 3) && (w2 >> 2) < len2) l2[row * len2 + (w2 >> 2)] = v2;
-                }
-            }
-        }
-    }
-}
-
-// gradient of corr level 0 at (row, w2) with the pooled levels folded in
-struct CorrGrad {
-    const float *l0, *l1, *l2;
-    int W2, len1, len2;
-    __device__ __forceinline__ float at(size_t row, int w2) const {
-        float v = l0[row * W2 + w2];
-        if (l1 && (w2 >> 1) < len1) v = fmaf(0.5f, l1[row * len1 + (w2 >> 1)], v);
-        if (l2 && (w2 >> 2) < len2) v = fmaf(0.25f, l2[row * len2 + (w2 >> 2)], v);
-        return v;
-    }
-};
-
-// which = 0: g_fmap1[c][w1] = sum_w2 G[w1][w2] fmap2[c][w2]   (grid.x over w1 tiles, the sum runs over w2)
-// which = 1: g_fmap2[c][w2] = sum_w1 G[w1][w2] fmap1[c][w1]   (grid.x over w2 tiles, the sum runs over w1)
-// D[row = c][col = the output column]; the k index of step s of a 16-wide slab is 4 (l >> 4) + s for both operands.
-__global__ __launch_bounds__(GC_THREADS) void geo_corr_bwd_kernel(const float* __restrict__ gcpyr, const float* __restrict__ fother,
-                                                                  float* __restrict__ gf, int B, int C, int H, int W1, int W2,
-                                                                  int levels, int which) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int o0 = (int)blockIdx.x * 16, h = (int)blockIdx.y, b = (int)blockIdx.z;
-    const int Wo = which ? W2 : W1, Wk = which ? W1 : W2;              // output columns, summed columns
-    const size_t rows = (size_t)B * H * W1;
-    CorrGrad G;
-    G.W2 = W2; G.len1 = W2 >> 1; G.len2 = W2 >> 2;
-    G.l0 = gcpyr;
-    G.l1 = levels > 1 ? gcpyr + geo_level_offset((long long)rows, W2, 1, 1) : nullptr;
-    G.l2 = levels > 2 ? gcpyr + geo_level_offset((long long)rows, W2, 1, 2) : nullptr;
-    const size_t HWk = (size_t)H * Wk, HWo = (size_t)H * Wo;
-    const float* frow = fother + (size_t)b * C * HWk + (size_t)h * Wk;
-    float* grow = gf + (size_t)b * C * HWo + (size_t)h * Wo;
-    const size_t row0 = ((size_t)b * H + h) * W1;
-    const int oc = o0 + li;                                             // this lane's output column (B operand)
-    for (int c0 = wave * 16; c0 < C; c0 += 64) {
-        f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-        const int ca = c0 + li;                                         // this lane's channel (A operand)
-        for (int k0 = 0; k0 < Wk; k0 += 16) {
-            float av[4], bv[4];
-            for (int sidx = 0; sidx < 4; ++sidx) {
-                const int k = k0 + 4 * lk + sidx;
-                const bool k_ok = k < Wk;
-                av[sidx] = (k_ok && ca < C) ? frow[(size_t)ca * HWk + k] : 0.f;
-                bv[sidx] = (k_ok && oc < Wo) ? (which ? G.at(row0 + k, oc) : G.at(row0 + oc, k)) : 0.f;
-            }
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
-        }
-        for (int r = 0; r < 4; ++r) {
-            const int c = c0 + 4 * lk + r;
-            if (c < C && oc < Wo) grow[(size_t)c * HWo + oc] = acc0[r] + acc1[r];
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ context_upsample
 // one lane per (b, Y, x): the four output pixels X = 4x .. 4x + 3 of row Y share the low-resolution cell (Y / 4, x)
 __global__ __launch_bounds__(CU_THREADS) void context_upsample_kernel(const float* __restrict__ disp, const float* __restrict__ wts,
@@ -433,9 +311,7 @@ extern "C" int stx_geo_corr_fwd(const float* fmap1, const float* fmap2, float* c
     STX_REQUIRE(B > 0 && C > 0 && H > 0 && W1 > 0 && W2 > 0 && B < 65536 && H < 65536, "geo_corr_fwd: bad shape B=%d C=%d H=%d W1=%d W2=%d",
                 B, C, H, W1, W2);
     STX_REQUIRE(levels >= 1 && levels <= GL_MAX_LEVELS && (W2 >> (levels - 1)) >= 1, "geo_corr_fwd: %d levels on W2=%d", levels, W2);
-    hipLaunchKernelGGL(geo_corr_fwd_kernel, dim3(stx_cdiv(W1, 16), H, B), dim3(GC_THREADS), 0, (hipStream_t)stream, fmap1, fmap2, cpyr,
-                       B, C, H, W1, W2, levels);
-    return stx_check_launch("geo_corr_fwd");
+    return corr_pyramid_fwd_launch(fmap1, fmap2, cpyr, B, C, H, W1, W2, levels, 1.0f, stream, "geo_corr_fwd");
 }
 
 extern "C" int stx_geo_corr_bwd(const float* gcpyr, const float* fmap1, const float* fmap2, float* gfmap1, float* gfmap2, int B, int C,
@@ -445,17 +321,7 @@ extern "C" int stx_geo_corr_bwd(const float* gcpyr, const float* fmap1, const fl
     STX_REQUIRE(B > 0 && C > 0 && H > 0 && W1 > 0 && W2 > 0 && B < 65536 && H < 65536, "geo_corr_bwd: bad shape B=%d C=%d H=%d W1=%d W2=%d",
                 B, C, H, W1, W2);
     STX_REQUIRE(levels >= 1 && levels <= GL_MAX_LEVELS && (W2 >> (levels - 1)) >= 1, "geo_corr_bwd: %d levels on W2=%d", levels, W2);
-    if (gfmap1) {
-        hipLaunchKernelGGL(geo_corr_bwd_kernel, dim3(stx_cdiv(W1, 16), H, B), dim3(GC_THREADS), 0, (hipStream_t)stream, gcpyr, fmap2,
-                           gfmap1, B, C, H, W1, W2, levels, 0);
-        if (int rc = stx_check_launch("geo_corr_bwd (fmap1)")) return rc;
-    }
-    if (gfmap2) {
-        hipLaunchKernelGGL(geo_corr_bwd_kernel, dim3(stx_cdiv(W2, 16), H, B), dim3(GC_THREADS), 0, (hipStream_t)stream, gcpyr, fmap1,
-                           gfmap2, B, C, H, W1, W2, levels, 1);
-        if (int rc = stx_check_launch("geo_corr_bwd (fmap2)")) return rc;
-    }
-    return STX_OK;
+    return corr_pyramid_bwd_launch(gcpyr, fmap1, fmap2, gfmap1, gfmap2, B, C, H, W1, W2, levels, 1.0f, stream, "geo_corr_bwd");
 }
 
 extern "C" int stx_geo_pyramid_fwd(const float* vol, float* gpyr, int B, int D, int H, int W, int C, int levels, void* stream) {

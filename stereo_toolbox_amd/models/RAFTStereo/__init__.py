@@ -1,0 +1,1 @@
+from .corr import CorrBlock1D, CorrBlockFast1D, PytorchAlternateCorrBlock1D  # noqa: F401

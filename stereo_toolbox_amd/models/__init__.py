@@ -8,6 +8,8 @@ from .PCWNet import PCWNet_G, PCWNet_GC  # noqa: F401
 from .CFNet import CFNet  # noqa: F401
 from . import IGEVStereo  # noqa: F401  (initial-volume entry points only)
 from . import FoundationStereo  # noqa: F401  (normalised initial volume only)
+from . import RAFTStereo  # noqa: F401  (correlation blocks only)
+from . import DEFOMStereo  # noqa: F401  (correlation block only)
 
 
 def load_checkpoint_flexible(model, checkpoint_path, state_dict_key=None):

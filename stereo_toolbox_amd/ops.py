@@ -1596,7 +1596,8 @@ def geo_pyramid_floats(rows, length, channels, levels):
 
 
 class _PyramidGrads:
-    """The gradient buffers of the two pyramids of one `Combined_Geo_Encoding_Volume`, shared by all of its lookups within
+    """The gradient buffers of the two pyramids of one `Combined_Geo_Encoding_Volume` (or of the one pyramid of a RAFT-family
+    `CorrBlock1D`, Corr1dLookupFn below), shared by all of its lookups within
     one backward pass: stx_geo_lookup_bwd ADDS into the rows a pixel owns, so the 22-32 lookups of a training step
     accumulate in place instead of handing autograd one dense pyramid-sized tensor per iteration.  The hand-off: the lookups
     do not read the pyramid tensors the build node returns (the public `geo_volume_pyramid` / `init_corr_pyramid`) but
@@ -1610,14 +1611,13 @@ class _PyramidGrads:
     def __init__(self):
         self.task, self.bufs = None, None
 
-    def take(self, n_geo, n_corr, device):
-        """(first lookup of this backward pass?, (ggpyr, gcpyr))"""
+    def take(self, device, *sizes):
+        """(first lookup of this backward pass?, one zeroed buffer per size: (ggpyr, gcpyr) / (gcpyr,))"""
         task = torch._C._current_graph_task_id()
         first = self.bufs is None or task != self.task
         if first:
             self.task = task
-            self.bufs = (torch.zeros(n_geo, dtype=torch.float32, device=device),
-                         torch.zeros(n_corr, dtype=torch.float32, device=device))
+            self.bufs = tuple(torch.zeros(n, dtype=torch.float32, device=device) for n in sizes)
         return first, self.bufs
 
     def release(self):
@@ -1747,7 +1747,7 @@ class GeoLookupFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         disp, coords = ctx.saved_tensors
-        first, (ggp, gcp) = ctx.grads.take(*ctx.sizes, disp.device)
+        first, (ggp, gcp) = ctx.grads.take(disp.device, *ctx.sizes)
         _call("stx_geo_lookup_bwd", _p(gout.contiguous()), _p(disp), _p(coords), _p(ggp), _p(gcp), *ctx.cfg)
         if first:
             return ggp, gcp, None, None, None, None
@@ -1771,6 +1771,129 @@ def geo_lookup(gpyr, cpyr, disp, coords, cfg, grads):
     if torch.is_grad_enabled() and (gpyr.requires_grad or cpyr.requires_grad):
         return GeoLookupFn.apply(gpyr, cpyr, disp, coords, cfg, grads)
     return GeoLookupFn.forward(_NoCtx(), gpyr, cpyr, disp, coords, cfg, None)
+
+
+# --------------------------------------------------------------------------------------- RAFT-family 1-D correlation lookup
+def corr1d_pyramid_floats(rows, W2, levels):
+    """Floats of the pixel-major correlation pyramid of csrc/corr1d.hip: level i is [rows][W2 >> i]."""
+    n = int(get_lib().raw("stx_corr1d_pyramid_floats")(rows, W2, levels))
+    if n <= 0:
+        raise StxError(f"correlation pyramid: bad shape rows={rows} W2={W2} num_levels={levels} (1..4 levels)")
+    return n
+
+
+class Corr1dPyramidFn(torch.autograd.Function):
+    """RAFTStereo/corr.py:110-125, 148-156: all-pairs row correlation / sqrt(C) (MFMA) with its pooled levels, one launch;
+    fmaps NCHW -> the flat pixel-major pyramid."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, levels):
+        B, C, H, W1 = f1.shape
+        W2 = f2.shape[3]
+        scale = 1.0 / float(C) ** 0.5
+        cpyr = torch.empty(corr1d_pyramid_floats(B * H * W1, W2, levels), dtype=torch.float32, device=f1.device)
+        _call("stx_corr1d_pyramid_fwd", _p(f1), _p(f2), _p(cpyr), B, C, H, W1, W2, levels, scale)
+        ctx.save_for_backward(f1, f2)
+        ctx.cfg = (B, C, H, W1, W2, levels, scale)
+        return cpyr
+
+    @staticmethod
+    def backward(ctx, gcp):
+        f1, f2 = ctx.saved_tensors
+        gf1 = torch.empty_like(f1) if ctx.needs_input_grad[0] else None
+        gf2 = torch.empty_like(f2) if ctx.needs_input_grad[1] else None
+        _call("stx_corr1d_pyramid_bwd", _p(gcp.contiguous()), _p(f1), _p(f2), _p(gf1), _p(gf2), *ctx.cfg)
+        return gf1, gf2, None
+
+
+class Corr1dHubFn(torch.autograd.Function):
+    """GeoPyramidHubFn for the one pyramid of a CorrBlock1D: an alias that only the lookups read (see _PyramidGrads)."""
+
+    @staticmethod
+    def forward(ctx, cpyr, grads):
+        ctx.grads = grads
+        return cpyr.view_as(cpyr)
+
+    @staticmethod
+    def backward(ctx, gcp):
+        ctx.grads.release()
+        return gcp, None
+
+
+def _corr1d_fmaps(fmap1, fmap2, who):
+    f1, f2 = channel_major(fmap1), channel_major(fmap2)
+    _chk(f1, "fmap1", 4)
+    _chk(f2, "fmap2", 4)
+    if f1.shape[:3] != f2.shape[:3]:
+        raise StxError(f"{who}: feature maps {tuple(f1.shape)} / {tuple(f2.shape)} do not match")
+    return f1, f2
+
+
+@fp32_region
+def corr1d_pyramid(fmap1, fmap2, levels, who="CorrBlock1D"):
+    """fmap1 [B, C, H, W1], fmap2 [B, C, H, W2] -> the flat pyramid of `levels` levels (corr1d_pyramid_floats)."""
+    f1, f2 = _corr1d_fmaps(fmap1, fmap2, who)
+    if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad):
+        return Corr1dPyramidFn.apply(f1, f2, levels)
+    return Corr1dPyramidFn.forward(_NoCtx(), f1, f2, levels)
+
+
+def corr1d_lookup_pyramid(cpyr, grads):
+    """The pyramid tensor the lookups of one object read: `cpyr` itself where no graph is recorded, its alias behind
+    Corr1dHubFn otherwise."""
+    if torch.is_grad_enabled() and cpyr.requires_grad:
+        return Corr1dHubFn.apply(cpyr, grads)
+    return cpyr
+
+
+def _corr1d_jobs(jobs):
+    """((level, radius, alpha, mult), ...) -> (the host array of the C-ABI, number of jobs, output channels)"""
+    flat = [float(v) for job in jobs for v in job]
+    return (ctypes.c_float * max(1, len(flat)))(*flat), len(jobs), sum(2 * int(job[1]) + 1 for job in jobs)
+
+
+class Corr1dLookupFn(torch.autograd.Function):
+    """One call of a RAFT-family correlation block on stx_corr1d_lookup_fwd / _bwd: every job of the call in one launch.
+    cfg = (B, H, W1, W2, levels).  The gradient goes to the pyramid only, accumulated through `grads` (_PyramidGrads)."""
+
+    @staticmethod
+    def forward(ctx, cpyr, base, disp, jobs, cfg, grads):
+        B, H, W1, W2, levels = cfg
+        table, n, channels = _corr1d_jobs(jobs)
+        out = torch.empty(B, channels, H, W1, dtype=torch.float32, device=base.device)
+        _call("stx_corr1d_lookup_fwd", _p(cpyr), _p(base), _p(disp), table, n, _p(out), *cfg)
+        ctx.save_for_backward(base, disp)
+        ctx.cfg, ctx.jobs, ctx.grads, ctx.size = cfg, jobs, grads, cpyr.numel()
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        base, disp = ctx.saved_tensors
+        table, n, _ = _corr1d_jobs(ctx.jobs)
+        first, (gcp,) = ctx.grads.take(base.device, ctx.size)
+        _call("stx_corr1d_lookup_bwd", _p(gout.contiguous()), _p(base), _p(disp), table, n, _p(gcp), *ctx.cfg)
+        return (gcp if first else None), None, None, None, None, None
+
+
+@fp32_region
+def corr1d_lookup(cpyr, base, disp, jobs, cfg, grads, who="CorrBlock1D"):
+    """[B, sum_j (2 r_j + 1), H, W1]; base (and disp, or None): B * H * W1 values; jobs: ((level, radius, alpha, mult), ...),
+    sample positions (base - alpha * disp) * mult + k of the pixel's row of that level."""
+    B, H, W1 = cfg[:3]
+    for t in (base, disp):
+        if t is not None and torch.is_grad_enabled() and t.requires_grad:
+            raise StxError(f"{who}: the sampling positions must not require grad -- the lookup is differentiated with respect to "
+                           "the feature maps only, as in the reference, which detaches them before every call "
+                           "(raft_stereo.py:154, defom_stereo.py:142); pass coords.detach() / disp.detach()")
+        if t is not None and t.numel() != B * H * W1:
+            raise StxError(f"{who}: positions {tuple(t.shape)} do not match the pyramid's {B} x {H} x {W1} pixels")
+    base = base.detach().contiguous()
+    disp = None if disp is None else disp.detach().contiguous()
+    _chk(base, "coords")
+    _chk(disp, "disp")
+    if torch.is_grad_enabled() and cpyr.requires_grad:
+        return Corr1dLookupFn.apply(cpyr, base, disp, jobs, cfg, grads)
+    return Corr1dLookupFn.forward(_NoCtx(), cpyr, base, disp, jobs, cfg, None)
 
 
 class ContextUpsampleFn(torch.autograd.Function):
