@@ -390,6 +390,37 @@ int stx_corr1d_lookup_fwd(const float* cpyr, const float* base, const float* dis
 int stx_corr1d_lookup_bwd(const float* gout, const float* base, const float* disp, const float* jobs, int njobs, float* gcpyr,
                           int B, int H, int W1, int W2, int levels, void* stream);
 
+/* ---- allpairs.hip: StereoAnywhere's volume stage on a row-wise all-pairs volume vol [B][H][W1][W2] -------------------------
+ * The four estimates regressed from the volume (models/StereoAnywhere/utils/utils.py:112-170), W1 != W2 allowed:
+ *   p_l = softmax over w2:  disp_l [B][H][W1] = w1 - sum_w2 p_l w2,  conf_l = 1 + sum_w2 p_l log2(p_l + 1e-6) / log2(W2)
+ *   p_r = softmax over w1:  disp_r [B][H][W2] = sum_w1 p_r w1 - w2,  conf_r = 1 + sum_w1 p_r log2(p_r + 1e-6) / log2(W1)
+ * stx_allpairs_estimates_fwd: `which` is a mask of bits 1 (disp_l), 2 (conf_l), 4 (disp_r), 8 (conf_r); exactly the outputs it
+ *   names are non-NULL, the others are NULL and cost nothing (a direction neither of whose outputs is asked for is not run).
+ *   stats (NULL for a plain forward): 4 * (B*H*W1 + B*H*W2) floats, per row and then per column (max, sum of exp, first moment,
+ *   entropy-slope moment); the part of a direction is written when that direction runs.  The volume is not transposed.
+ * stx_allpairs_estimates_bwd: any of the four gradients may be NULL (not all); those given must belong to directions the
+ *   forward that wrote `stats` ran.  gvol [B][H][W1][W2]: every element written once = row-direction + column-direction softmax
+ *   Jacobian terms; no atomics, bitwise reproducible.
+ * Limits of the estimates: 2 <= W1 <= 512 and 2 <= W2 <= 512 (a volume row is held in registers), B*H*W1*W2 < 2^40.
+ * The volume-in correlation block (corr.py:75-132) and the truncation mask (truncate_corr_volume_v2, utils/utils.py:216-238):
+ * stx_corr1d_volume_pyramid_fwd: the pyramid of corr1d.hip above (same layout, stx_corr1d_pyramid_floats(B*H*W1, W2, levels)
+ *   floats, levels 1..4, last level >= 2 positions, any W1 / W2) with level 0 = vol, times
+ *   (1 - c) + c * (sigmoid((w1 - tdisp) - w2) * (1 - atten) + atten), c = tconf, when tdisp / tconf [B*H*W1] are given (both or
+ *   neither); the pooled levels are pairwise means of the level before; everything in one launch.
+ * stx_corr1d_volume_pyramid_bwd: gcpyr (gradient of every level) -> gvol, every element written, the factor applied; tdisp and
+ *   tconf carry no gradient (the reference detaches the mask, stereoanywhere.py:235).
+ * stx_truncate_mask_fwd: the mask volume [B][1][H][W][W] itself, same expression; has_th != 0: c = (conf > conf_th). */
+int stx_allpairs_estimates_fwd(const float* vol, int which, float* disp_l, float* conf_l, float* disp_r, float* conf_r, float* stats,
+                               int B, int H, int W1, int W2, void* stream);
+int stx_allpairs_estimates_bwd(const float* g_disp_l, const float* g_conf_l, const float* g_disp_r, const float* g_conf_r,
+                               const float* vol, const float* stats, float* gvol, int B, int H, int W1, int W2, void* stream);
+int stx_corr1d_volume_pyramid_fwd(const float* vol, const float* tdisp, const float* tconf, float atten, float* cpyr, int B, int H,
+                                  int W1, int W2, int levels, void* stream);
+int stx_corr1d_volume_pyramid_bwd(const float* gcpyr, const float* tdisp, const float* tconf, float atten, float* gvol, int B, int H,
+                                  int W1, int W2, int levels, void* stream);
+int stx_truncate_mask_fwd(const float* disp, const float* conf, int has_th, float conf_th, float atten, float* mask, int B, int H,
+                          int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,12 @@ SIGNATURES = {
     "stx_corr1d_pyramid_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "stx_corr1d_lookup_fwd": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     "stx_corr1d_lookup_bwd": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    # allpairs.hip
+    "stx_allpairs_estimates_fwd": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_allpairs_estimates_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_corr1d_volume_pyramid_fwd": [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
+    "stx_corr1d_volume_pyramid_bwd": [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
+    "stx_truncate_mask_fwd": [_P, _P, _I, _F, _F, _P, _I, _I, _I, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

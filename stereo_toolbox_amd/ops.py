@@ -1896,6 +1896,139 @@ def corr1d_lookup(cpyr, base, disp, jobs, cfg, grads, who="CorrBlock1D"):
     return Corr1dLookupFn.forward(_NoCtx(), cpyr, base, disp, jobs, cfg, None)
 
 
+# --------------------------------------------------------------------------------------- StereoAnywhere volume stage
+ALLPAIRS_DISP_LEFT, ALLPAIRS_CONF_LEFT, ALLPAIRS_DISP_RIGHT, ALLPAIRS_CONF_RIGHT = 1, 2, 4, 8
+ALLPAIRS_ALL = 15
+ALLPAIRS_MAX_W = 512                                                     # csrc/allpairs.hip AP_MAX_W
+
+
+class AllpairsEstimatesFn(torch.autograd.Function):
+    """The estimates of StereoAnywhere/utils/utils.py:112-170 named by the bit mask `which`, from vol [B, H, W1, W2], on
+    stx_allpairs_estimates_fwd / _bwd: one tensor per set bit, in bit order ([B, H, W1] left, [B, H, W2] right); ONE backward
+    launch for all of them."""
+
+    @staticmethod
+    def forward(ctx, vol, which):
+        B, H, W1, W2 = vol.shape
+        outs = [torch.empty(B, H, W2 if bit & 12 else W1, dtype=torch.float32, device=vol.device) if which & bit else None
+                for bit in (1, 2, 4, 8)]
+        stats = None
+        if not isinstance(ctx, _NoCtx):
+            stats = torch.empty(4 * (B * H * W1 + B * H * W2), dtype=torch.float32, device=vol.device)
+            ctx.set_materialize_grads(False)                             # an output the loss does not use: NULL, not zeros
+        _call("stx_allpairs_estimates_fwd", _p(vol), which, *(_p(o) for o in outs), _p(stats), B, H, W1, W2)
+        ctx.save_for_backward(vol, stats)
+        ctx.which = which
+        return tuple(o for o in outs if o is not None)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        vol, stats = ctx.saved_tensors
+        B, H, W1, W2 = vol.shape
+        it = iter(gouts)
+        grads = [next(it) if ctx.which & bit else None for bit in (1, 2, 4, 8)]
+        grads = [None if g is None else g.contiguous() for g in grads]
+        gvol = torch.empty_like(vol)
+        _call("stx_allpairs_estimates_bwd", *(_p(g) for g in grads), _p(vol), _p(stats), _p(gvol), B, H, W1, W2)
+        return gvol, None
+
+
+@fp32_region
+def allpairs_estimates(volume, which=ALLPAIRS_ALL):
+    """volume [B, 1, H, W1, W2] (or [B, H, W1, W2]) -> (disp_left, conf_left, disp_right, conf_right), each [B, 1, H, W1] (left)
+    / [B, 1, H, W2] (right) or None where its bit of `which` (ALLPAIRS_*) is not set.  2 <= W1, W2 <= 512."""
+    if volume.dim() == 5 and volume.shape[1] == 1:
+        vol = volume[:, 0]
+    elif volume.dim() == 4:
+        vol = volume
+    else:
+        raise StxError(f"allpairs_estimates: the volume must be [B, 1, H, W1, W2], got {tuple(volume.shape)}")
+    if not isinstance(which, int) or not 0 < which <= ALLPAIRS_ALL:
+        raise StxError(f"allpairs_estimates: `which` must be a mask of ALLPAIRS_* bits (1..15), got {which!r}")
+    vol = vol.contiguous()
+    _chk(vol, "volume", 4)
+    W1, W2 = vol.shape[2:]
+    if not (2 <= W1 <= ALLPAIRS_MAX_W and 2 <= W2 <= ALLPAIRS_MAX_W):
+        raise StxError(f"allpairs_estimates: W1={W1} / W2={W2} outside the supported 2..{ALLPAIRS_MAX_W}")
+    if torch.is_grad_enabled() and vol.requires_grad:
+        got = AllpairsEstimatesFn.apply(vol, which)
+    else:
+        got = AllpairsEstimatesFn.forward(_NoCtx(), vol, which)
+    it = iter(got)
+    return tuple(next(it).unsqueeze(1) if which & bit else None for bit in (1, 2, 4, 8))
+
+
+def _truncate_args(truncate, B, H, W1, who):
+    """(disp_left, conf_left, attenuation_gain) -> (tdisp, tconf, atten): detached dense fp32 [B*H*W1] maps."""
+    if truncate is None:
+        return None, None, 0.0
+    disp, conf, atten = truncate
+    for t, name in ((disp, "disp_left"), (conf, "conf_left")):
+        if t.numel() != B * H * W1:
+            raise StxError(f"{who}: truncate {name} {tuple(t.shape)} does not match the volume's {B} x {H} x {W1} pixels")
+    disp, conf = disp.detach().contiguous(), conf.detach().contiguous()
+    _chk(disp, "disp_left")
+    _chk(conf, "conf_left")
+    return disp, conf, float(atten)
+
+
+class Corr1dVolumePyramidFn(torch.autograd.Function):
+    """StereoAnywhere/corr.py:85-91: the flat pixel-major pyramid whose level 0 is the given volume [B, H, W1, W2] (times the
+    truncation factor where tdisp / tconf are given), one launch; differentiated with respect to the volume."""
+
+    @staticmethod
+    def forward(ctx, vol, tdisp, tconf, atten, levels):
+        B, H, W1, W2 = vol.shape
+        cpyr = torch.empty(corr1d_pyramid_floats(B * H * W1, W2, levels), dtype=torch.float32, device=vol.device)
+        _call("stx_corr1d_volume_pyramid_fwd", _p(vol), _p(tdisp), _p(tconf), atten, _p(cpyr), B, H, W1, W2, levels)
+        ctx.save_for_backward(tdisp, tconf)
+        ctx.cfg = (atten, B, H, W1, W2, levels)
+        return cpyr
+
+    @staticmethod
+    def backward(ctx, gcp):
+        tdisp, tconf = ctx.saved_tensors
+        atten, B, H, W1, W2, levels = ctx.cfg
+        gvol = torch.empty(B, H, W1, W2, dtype=torch.float32, device=gcp.device)
+        _call("stx_corr1d_volume_pyramid_bwd", _p(gcp.contiguous()), _p(tdisp), _p(tconf), atten, _p(gvol), B, H, W1, W2, levels)
+        return gvol, None, None, None, None
+
+
+@fp32_region
+def corr1d_volume_pyramid(volume, levels, truncate=None, who="CorrBlock1D"):
+    """volume [B, H, W1, 1, W2] (or [B, H, W1, W2]) -> the flat pyramid of `levels` levels (corr1d_pyramid_floats) with level 0 =
+    the volume; truncate = (disp_left, conf_left, attenuation_gain) multiplies it by truncate_mask(..., conf_th=None) on the fly
+    (the maps carry no gradient)."""
+    if volume.dim() == 5 and volume.shape[3] == 1:
+        vol = volume.squeeze(3)
+    elif volume.dim() == 4:
+        vol = volume
+    else:
+        raise StxError(f"{who}: the volume must be [B, H, W1, 1, W2], got {tuple(volume.shape)}")
+    vol = vol.contiguous()
+    _chk(vol, "fullcorr", 4)
+    B, H, W1, W2 = vol.shape
+    tdisp, tconf, atten = _truncate_args(truncate, B, H, W1, who)
+    if torch.is_grad_enabled() and vol.requires_grad:
+        return Corr1dVolumePyramidFn.apply(vol, tdisp, tconf, atten, levels)
+    return Corr1dVolumePyramidFn.forward(_NoCtx(), vol, tdisp, tconf, atten, levels)
+
+
+@fp32_region
+def truncate_mask(disp_left, conf_left, conf_th=0.5, attenuation_gain=0.1):
+    """truncate_corr_volume_v2 (StereoAnywhere/utils/utils.py:216-238): disp_left, conf_left [B, 1, H, W] -> [B, 1, H, W, W]
+    (1 - c) + c (sigmoid((w - disp) - w') (1 - gain) + gain), c = conf_left or, with a threshold, conf_left > conf_th.  No
+    gradient: the model detaches the mask (stereoanywhere.py:235)."""
+    if disp_left.dim() != 4 or disp_left.shape[1] != 1 or conf_left.shape != disp_left.shape:
+        raise StxError(f"truncate_mask: disp_left / conf_left must be [B, 1, H, W], got {tuple(disp_left.shape)} / "
+                       f"{tuple(conf_left.shape)}")
+    B, _, H, W = disp_left.shape
+    disp, conf, atten = _truncate_args((disp_left, conf_left, attenuation_gain), B, H, W, "truncate_mask")
+    mask = torch.empty(B, 1, H, W, W, dtype=torch.float32, device=disp.device)
+    _call("stx_truncate_mask_fwd", _p(disp), _p(conf), int(conf_th is not None), float(conf_th or 0.0), atten, _p(mask), B, H, W)
+    return mask
+
+
 class ContextUpsampleFn(torch.autograd.Function):
     """context_upsample (IGEVStereo/submodule.py:243-255) on stx_context_upsample_fwd / _bwd."""
 
