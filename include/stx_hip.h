@@ -421,6 +421,46 @@ int stx_corr1d_volume_pyramid_bwd(const float* gcpyr, const float* tdisp, const 
 int stx_truncate_mask_fwd(const float* disp, const float* conf, int has_th, float conf_th, float atten, float* mask, int B, int H,
                           int W, void* stream);
 
+/* ---- selfsup_loss.hip: the self-supervised objective (reference loss_functions/), NCHW fp32 ----------------------------------
+ * All reductions are deterministic (no float atomics, sums in double); every output element is written once.
+ * stx_photo_warp_fwd (photometric_loss.py:5-37): warped [B][C][H][W] = right sampled bilinearly in both directions, zeros
+ *   outside, at x = (w - disp) W / (W - 1) - 1/2, y = h H / (H - 1) - 1/2 (the reference's linspace grid under
+ *   align_corners=False -- NOT stx_warp_fwd); valid [B][H][W] = the summed weight of the corners inside the image.  H, W >= 2.
+ * stx_photo_warp_bwd: gdisp [B][H][W] = -W / (W - 1) sum_c gwarped d warped / d x.  The image gets no gradient.
+ * stx_ssim_fwd (:40-77): out [B][C][H][W] = clamp((1 - SSIM) / 2, 0, 1) over window x window boxes of the reflect-padded images;
+ *   window odd, 3..11, H and W > window / 2.  The moments are summed in double.
+ * stx_ssim_bwd: gx / gy (either may be NULL) from g_out; workspace = stx_ssim_bwd_workspace_floats floats (coefficient maps).
+ * stx_photometric_fwd (:80-104): loss [B][1][H][W] = mean_C((w ssim(left, Y) + (1 - w) |left - Y|) valid), window 7,
+ *   Y = the warp of right by disp, or right itself when disp is NULL (then enable_mask must be 0); valid only with enable_mask.
+ * stx_photometric_bwd: gdisp [B][1][H][W] from gloss, through SSIM, the L1 term and the warp; workspace =
+ *   stx_photometric_bwd_workspace_floats floats.  disp must be given.
+ * stx_auto_mask_fwd (auto_mask.py:7-17): mask [B][1][H][W] (bytes 0 / 1) = photometric(disp) < photometric(NULL), both without
+ *   valid, w = 0.85; denorm != 0 (C = 3) applies x * std + mean of ImageNet to both images first.
+ * stx_smoothness_fwd (smoothness_loss.py:5-44): out[0] = mean |dx n| exp(-mean_C |dx img|) + mean |dy n| exp(-mean_C |dy img|),
+ *   n = disp / (per-image mean + 1e-7); out[1] = max of img (the caller's range warning, no extra pass); stats = 4 B floats
+ *   (2 B doubles: per-image mean and share of the loss) for the backward; workspace = stx_smoothness_workspace_floats floats.
+ *   stats and workspace 8-byte aligned.  H, W >= 2.
+ * stx_smoothness_bwd: gdisp [B][1][H][W] from the scalar gout (a device pointer), the path through the per-image mean included. */
+int stx_photo_warp_fwd(const float* right, const float* disp, float* warped, float* valid, int B, int C, int H, int W, void* stream);
+int stx_photo_warp_bwd(const float* gwarped, const float* right, const float* disp, float* gdisp, int B, int C, int H, int W,
+                       void* stream);
+int stx_ssim_fwd(const float* x, const float* y, float* out, int B, int C, int H, int W, int window, void* stream);
+long long stx_ssim_bwd_workspace_floats(int B, int C, int H, int W);
+int stx_ssim_bwd(const float* g_out, const float* x, const float* y, float* gx, float* gy, float* workspace, int B, int C, int H, int W,
+                 int window, void* stream);
+int stx_photometric_fwd(const float* left, const float* right, const float* disp, double ssim_weight, int enable_mask, float* loss,
+                        int B, int C, int H, int W, void* stream);
+long long stx_photometric_bwd_workspace_floats(int B, int C, int H, int W);
+int stx_photometric_bwd(const float* gloss, const float* left, const float* right, const float* disp, double ssim_weight,
+                        int enable_mask, float* gdisp, float* workspace, int B, int C, int H, int W, void* stream);
+int stx_auto_mask_fwd(const float* left, const float* right, const float* disp, int denorm, unsigned char* mask, int B, int C, int H,
+                      int W, void* stream);
+long long stx_smoothness_workspace_floats(int B, int H, int W);
+int stx_smoothness_fwd(const float* disp, const float* img, float* out, float* stats, float* workspace, int B, int C, int H, int W,
+                       void* stream);
+int stx_smoothness_bwd(const float* gout, const float* disp, const float* img, const float* stats, float* gdisp, int B, int C, int H,
+                       int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

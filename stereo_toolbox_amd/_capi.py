@@ -114,6 +114,19 @@ SIGNATURES = {
     "stx_corr1d_volume_pyramid_fwd": [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
     "stx_corr1d_volume_pyramid_bwd": [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
     "stx_truncate_mask_fwd": [_P, _P, _I, _F, _F, _P, _I, _I, _I, _P],
+    # selfsup_loss.hip
+    "stx_photo_warp_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_photo_warp_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_ssim_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "stx_ssim_bwd_workspace_floats": [_I, _I, _I, _I],
+    "stx_ssim_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "stx_photometric_fwd": [_P, _P, _P, ctypes.c_double, _I, _P, _I, _I, _I, _I, _P],
+    "stx_photometric_bwd_workspace_floats": [_I, _I, _I, _I],
+    "stx_photometric_bwd": [_P, _P, _P, _P, ctypes.c_double, _I, _P, _P, _I, _I, _I, _I, _P],
+    "stx_auto_mask_fwd": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P],
+    "stx_smoothness_workspace_floats": [_I, _I, _I],
+    "stx_smoothness_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_smoothness_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

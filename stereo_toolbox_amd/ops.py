@@ -1194,6 +1194,9 @@ class _NoCtx:
     def save_for_backward(self, *a):
         pass
 
+    def mark_non_differentiable(self, *a):
+        pass
+
 
 # --------------------------------------------------------------------------------------- PCWNet / CFNet 2-D helpers (row f-1)
 class WarpFn(torch.autograd.Function):
@@ -2063,3 +2066,220 @@ def context_upsample(disp_low, up_weights):
     if torch.is_grad_enabled() and (disp_low.requires_grad or up_weights.requires_grad):
         return ContextUpsampleFn.apply(disp_low, up_weights)
     return ContextUpsampleFn.forward(_NoCtx(), disp_low, up_weights)
+
+
+# --------------------------------------------------------------------------------------- self-supervised losses
+SSIM_WINDOWS = (3, 5, 7, 9, 11)                                          # csrc/selfsup_loss.hip SL_MAX_PAD
+PHOTO_WINDOW = 7                                                         # photometric_loss calls ssim() with its default
+
+
+def _images_are_data(who, **images):
+    """The images of the self-supervised losses carry no gradient (as the positions of corr1d_lookup): one that asks for it raises."""
+    for name, t in images.items():
+        if t is not None and t.requires_grad and torch.is_grad_enabled():
+            raise StxError(f"{who}: {name} requires grad, but the images are data here (no image gradient is built) -- detach() it")
+
+
+def _image_pair(who, left, right, names=("left_image", "right_image")):
+    left, right = left.contiguous(), right.contiguous()
+    _chk(left, names[0])
+    _chk(right, names[1])
+    if left.dim() != 4 or left.shape != right.shape:
+        raise StxError(f"{who}: {names[0]} / {names[1]} must be two [B, C, H, W] tensors of one shape, got {tuple(left.shape)} / "
+                       f"{tuple(right.shape)}")
+    return left, right
+
+
+def _disp_map(who, disp, like):
+    disp = disp.contiguous()
+    _chk(disp, "disp")
+    B, _, H, W = like.shape
+    if disp.shape != (B, 1, H, W):
+        raise StxError(f"{who}: disp must be [B, 1, H, W] = {(B, 1, H, W)}, got {tuple(disp.shape)}")
+    if H < 2 or W < 2:
+        raise StxError(f"{who}: the reference's sampling grid needs H, W >= 2, got {H} x {W}")
+    return disp
+
+
+def _window_fits(who, H, W, window):
+    if H <= window // 2 or W <= window // 2:
+        raise StxError(f"{who}: reflect padding by {window // 2} needs H, W > {window // 2}, got {H} x {W}")
+
+
+class PhotoWarpFn(torch.autograd.Function):
+    """warp_right_to_left (loss_functions/photometric_loss.py:5-37) on stx_photo_warp_fwd / _bwd; gradient to disp only."""
+
+    @staticmethod
+    def forward(ctx, right, disp):
+        B, C, H, W = right.shape
+        warped = torch.empty_like(right)
+        valid = torch.empty(B, 1, H, W, dtype=torch.float32, device=right.device)
+        _call("stx_photo_warp_fwd", _p(right), _p(disp), _p(warped), _p(valid), B, C, H, W)
+        ctx.save_for_backward(right, disp)
+        ctx.mark_non_differentiable(valid)
+        return warped, valid
+
+    @staticmethod
+    def backward(ctx, g, _gvalid):
+        right, disp = ctx.saved_tensors
+        B, C, H, W = right.shape
+        gdisp = torch.empty_like(disp)
+        _call("stx_photo_warp_bwd", _p(g.contiguous()), _p(right), _p(disp), _p(gdisp), B, C, H, W)
+        return None, gdisp
+
+
+@fp32_region
+def photo_warp(right_image, disp):
+    """right_image [B, C, H, W], disp [B, 1, H, W] -> (warped, valid_mask), both [B, C, H, W] (the mask a broadcast view): the right
+    image sampled at x = (w - disp) W / (W - 1) - 1/2, y = h H / (H - 1) - 1/2, bilinear with zeros outside -- the reference's
+    linspace grid under align_corners=False, not `warp` above.  valid_mask is the summed weight of the in-image corners and carries
+    no gradient; warped is differentiable in disp."""
+    who = "photo_warp"
+    right = right_image.contiguous()
+    _chk(right, "right_image", 4)
+    _images_are_data(who, right_image=right)
+    disp = _disp_map(who, disp, right)
+    if torch.is_grad_enabled() and disp.requires_grad:
+        warped, valid = PhotoWarpFn.apply(right, disp)
+    else:
+        warped, valid = PhotoWarpFn.forward(_NoCtx(), right, disp)
+    return warped, valid.expand_as(warped)
+
+
+class SsimDistanceFn(torch.autograd.Function):
+    """ssim (loss_functions/photometric_loss.py:40-77) on stx_ssim_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, x, y, window):
+        B, C, H, W = x.shape
+        out = torch.empty_like(x)
+        _call("stx_ssim_fwd", _p(x), _p(y), _p(out), B, C, H, W, window)
+        ctx.save_for_backward(x, y)
+        ctx.window = window
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        B, C, H, W = x.shape
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        ws = _WS.get("ssim_bwd", get_lib().raw("stx_ssim_bwd_workspace_floats")(B, C, H, W), x.device)
+        _call("stx_ssim_bwd", _p(g.contiguous()), _p(x), _p(y), _p(gx), _p(gy), _p(ws), B, C, H, W, ctx.window)
+        return gx, gy, None
+
+
+@fp32_region
+def ssim_distance(x, y, window_size=7, pad_mode="reflect"):
+    """x, y [B, C, H, W] -> [B, C, H, W] clamp((1 - SSIM) / 2, 0, 1) over window_size x window_size boxes of the reflect-padded
+    images; differentiable in both.  Odd windows 3 .. 11 and pad_mode 'reflect' only."""
+    who = "ssim_distance"
+    if pad_mode != "reflect":
+        raise StxError(f"{who}: pad_mode {pad_mode!r} is not built (only 'reflect')")
+    if not isinstance(window_size, int) or window_size not in SSIM_WINDOWS:
+        raise StxError(f"{who}: window_size {window_size!r} is not one of the odd sizes {SSIM_WINDOWS}")
+    x, y = _image_pair(who, x, y, ("x", "y"))
+    _window_fits(who, x.shape[2], x.shape[3], window_size)
+    if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return SsimDistanceFn.apply(x, y, window_size)
+    return SsimDistanceFn.forward(_NoCtx(), x, y, window_size)
+
+
+class PhotometricLossFn(torch.autograd.Function):
+    """photometric_loss (loss_functions/photometric_loss.py:80-104) on stx_photometric_fwd / _bwd; gradient to disp only."""
+
+    @staticmethod
+    def forward(ctx, left, right, disp, ssim_weight, enable_mask):
+        B, C, H, W = left.shape
+        loss = torch.empty(B, 1, H, W, dtype=torch.float32, device=left.device)
+        _call("stx_photometric_fwd", _p(left), _p(right), _p(disp), ssim_weight, int(enable_mask), _p(loss), B, C, H, W)
+        ctx.save_for_backward(left, right, disp)
+        ctx.cfg = (ssim_weight, int(enable_mask))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        left, right, disp = ctx.saved_tensors
+        B, C, H, W = left.shape
+        gdisp = torch.empty_like(disp)
+        ws = _WS.get("photometric_bwd", get_lib().raw("stx_photometric_bwd_workspace_floats")(B, C, H, W), left.device)
+        _call("stx_photometric_bwd", _p(g.contiguous()), _p(left), _p(right), _p(disp), *ctx.cfg, _p(gdisp), _p(ws), B, C, H, W)
+        return None, None, gdisp, None, None
+
+
+@fp32_region
+def photometric_loss(left_image, right_image, disp=None, ssim_weight=0.85, enable_mask=True):
+    """[B, 1, H, W] = mean_C((ssim_weight * ssim(left, warped) + (1 - ssim_weight) * |left - warped|) * valid_mask) with warped,
+    valid_mask = photo_warp(right_image, disp), in one launch; disp=None compares the images as they are (then there is no mask:
+    enable_mask must be False).  Differentiable in disp."""
+    who = "photometric_loss"
+    if disp is None and enable_mask:
+        raise StxError(f"{who}: enable_mask=True needs a disparity -- without a warp there is no valid_mask (pass enable_mask=False)")
+    left, right = _image_pair(who, left_image, right_image)
+    _images_are_data(who, left_image=left, right_image=right)
+    _window_fits(who, left.shape[2], left.shape[3], PHOTO_WINDOW)
+    if disp is not None:
+        disp = _disp_map(who, disp, left)
+    if disp is not None and torch.is_grad_enabled() and disp.requires_grad:
+        return PhotometricLossFn.apply(left, right, disp, float(ssim_weight), bool(enable_mask))
+    return PhotometricLossFn.forward(_NoCtx(), left, right, disp, float(ssim_weight), bool(enable_mask))
+
+
+@fp32_region
+def auto_mask(left_image, right_image, disp, denorm=False):
+    """bool [B, 1, H, W]: photometric_loss(left, right, disp) < photometric_loss(left, right), both with enable_mask=False
+    (loss_functions/auto_mask.py:7-17), one launch; denorm=True undoes the ImageNet normalisation of both images first (3
+    channels).  No gradient."""
+    who = "auto_mask"
+    left, right = _image_pair(who, left_image.detach(), right_image.detach())
+    if denorm and left.shape[1] != 3:
+        raise StxError(f"{who}: denorm=True is defined for 3 channels, got {left.shape[1]}")
+    _window_fits(who, left.shape[2], left.shape[3], PHOTO_WINDOW)
+    disp = _disp_map(who, disp.detach(), left)
+    B, C, H, W = left.shape
+    mask = torch.empty(B, 1, H, W, dtype=torch.bool, device=left.device)
+    _call("stx_auto_mask_fwd", _p(left), _p(right), _p(disp), int(bool(denorm)), _p(mask), B, C, H, W)
+    return mask
+
+
+class SmoothnessLossFn(torch.autograd.Function):
+    """smoothness_loss (loss_functions/smoothness_loss.py:5-44) on stx_smoothness_fwd / _bwd -> (loss, max of img), 0-d both."""
+
+    @staticmethod
+    def forward(ctx, disp, img):
+        B, C, H, W = img.shape
+        out = torch.empty(2, dtype=torch.float32, device=img.device)
+        stats = torch.empty(4 * B, dtype=torch.float32, device=img.device)
+        ws = _WS.get("smoothness", get_lib().raw("stx_smoothness_workspace_floats")(B, H, W), img.device)
+        _call("stx_smoothness_fwd", _p(disp), _p(img), _p(out), _p(stats), _p(ws), B, C, H, W)
+        ctx.save_for_backward(disp, img, stats)
+        loss, peak = out[0], out[1]
+        ctx.mark_non_differentiable(peak)
+        return loss, peak
+
+    @staticmethod
+    def backward(ctx, g, _gpeak):
+        disp, img, stats = ctx.saved_tensors
+        B, C, H, W = img.shape
+        gdisp = torch.empty_like(disp)
+        _call("stx_smoothness_bwd", _p(g.contiguous()), _p(disp), _p(img), _p(stats), _p(gdisp), B, C, H, W)
+        return gdisp, None
+
+
+@fp32_region
+def smoothness_loss(disp, img, warn=True):
+    """0-d tensor mean(|dx n| exp(-mean_C |dx img|)) + mean(|dy n| exp(-mean_C |dy img|)), n = disp / (per-image mean + 1e-7);
+    differentiable in disp (the term through the mean included).  warn=True prints the reference's warning when img.max() > 1 --
+    the max comes out of the same pass, but reading it is a device-to-host sync; warn=False never syncs."""
+    who = "smoothness_loss"
+    img = img.contiguous()
+    _chk(img, "img", 4)
+    _images_are_data(who, img=img)
+    disp = _disp_map(who, disp, img)
+    if torch.is_grad_enabled() and disp.requires_grad:
+        loss, peak = SmoothnessLossFn.apply(disp, img)
+    else:
+        loss, peak = SmoothnessLossFn.forward(_NoCtx(), disp, img)
+    if warn and float(peak) > 1.0:
+        print("Warning: Image may not be normalized. Expected range: [0,1]")
+    return loss
