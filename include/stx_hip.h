@@ -461,6 +461,35 @@ int stx_smoothness_fwd(const float* disp, const float* img, float* out, float* s
 int stx_smoothness_bwd(const float* gout, const float* disp, const float* img, const float* stats, float* gdisp, int B, int C, int H,
                        int W, void* stream);
 
+/* ---- sttr_head.hip: STTR's matching head (models/STTR/regression_head.py) on the raw cross-attention attn [N][H][W][W] ---------
+ * S = attn (-inf where the right position exceeds the left one) with a dustbin row and column holding *phi (a device scalar),
+ * M = W + 1.  mode 1: `iters` log-space Sinkhorn iterations per (n, h) with log mu = log nu = (log_one x W, log_bin) and
+ * P = exp(S + u + v + log_2w); mode 0: P = row softmax of S (iters and the three constants unused).  log_one = log(1 / 2W),
+ * log_bin = log(W / 2W), log_2w = log(2W) are formed by the CALLER in fp32, the way the reference forms them on the host.
+ * One workgroup per (n, h); no float atomics, bitwise reproducible.  Limits: 2 <= W <= 431, 1 <= iters <= 10, fp32 tensors only.
+ * Exponents and sums are formed in double; us / vs are doubles.
+ * stx_sttr_head_fwd: the fused head, P is never written.  Outputs [N][H][W]: disp = sum over the 3-wide window around the first
+ *   arg-max of P_j max(i - j, 0) / norm; norm = the window's sum, forced to 1 where occ_mask (bytes, NULL = none) is set or,
+ *   without a mask, where it is below 0.1; occ = 1 - norm; arg = the arg-max index, bit 16 set where norm was forced;
+ *   gt_response (with target, both or neither) = P sampled linearly at target between the clamped floor and ceil,
+ *   weight_r = target - clamped floor; bin_left = P[:W, W], bin_right = P[W, :W].  us / vs (both or neither, NULL for a plain
+ *   forward): mode 1 the scaling vectors u_k, v_k [N][H][iters][M], mode 0 the row max and row sum [N][H][M].
+ * stx_sttr_head_bwd: any of the five gradients may be NULL (not all).  g_attn [N][H][W][W] written once per element (exact
+ *   zeros at -inf entries); phi_partials [N*H] (doubles) = one partial per matrix, g_phi [1] = their sum in a fixed order.
+ * stx_sttr_transport_fwd / _bwd: the dense pair, P and G [N][H][M][M]; the same sweeps. */
+int stx_sttr_head_fwd(const float* attn, const float* phi, int mode, int iters, float log_one, float log_bin, float log_2w,
+                      const unsigned char* occ_mask, const float* target, float* disp, float* occ, float* norm, int* arg,
+                      float* gt_response, float* bin_left, float* bin_right, double* us, double* vs, int N, int H, int W, void* stream);
+int stx_sttr_head_bwd(const float* g_disp, const float* g_occ, const float* g_gt, const float* g_bin_left, const float* g_bin_right,
+                      const float* attn, const float* phi, int mode, int iters, float log_one, float log_bin, float log_2w,
+                      const float* target, const float* disp, const float* norm, const int* arg, const double* us, const double* vs,
+                      float* g_attn, double* phi_partials, float* g_phi, int N, int H, int W, void* stream);
+int stx_sttr_transport_fwd(const float* attn, const float* phi, int mode, int iters, float log_one, float log_bin, float log_2w,
+                           float* P, double* us, double* vs, int N, int H, int W, void* stream);
+int stx_sttr_transport_bwd(const float* G, const float* attn, const float* phi, int mode, int iters, float log_one, float log_bin,
+                           float log_2w, const double* us, const double* vs, float* g_attn, double* phi_partials, float* g_phi, int N,
+                           int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,11 @@ SIGNATURES = {
     "stx_smoothness_workspace_floats": [_I, _I, _I],
     "stx_smoothness_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "stx_smoothness_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    # sttr_head.hip
+    "stx_sttr_head_fwd": [_P, _P, _I, _I, _F, _F, _F] + [_P] * 11 + [_I, _I, _I, _P],
+    "stx_sttr_head_bwd": [_P] * 7 + [_I, _I, _F, _F, _F] + [_P] * 9 + [_I, _I, _I, _P],
+    "stx_sttr_transport_fwd": [_P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _I, _I, _I, _P],
+    "stx_sttr_transport_bwd": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

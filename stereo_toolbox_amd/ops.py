@@ -2283,3 +2283,168 @@ def smoothness_loss(disp, img, warn=True):
     if warn and float(peak) > 1.0:
         print("Warning: Image may not be normalized. Expected range: [0,1]")
     return loss
+
+
+# --------------------------------------------------------------------------------------- STTR matching head
+STTR_MAX_W = 431                                                         # csrc/sttr_head.hip ST_MAX_W
+STTR_MAX_ITERS = 10                                                      # ... ST_MAX_ITERS
+_STTR_CONSTANTS = {}
+
+
+def _sttr_constants(W):
+    """(log(1 / 2W), log(W / 2W), log(2W)) as the reference forms them: fp32 tensors on the host (regression_head.py:176-188),
+    also in an fp64 run.  Passed to the kernels as arguments, so no device logf of a constant enters the comparison."""
+    c = _STTR_CONSTANTS.get(W)
+    if c is None:
+        log_marginal = (torch.cat([torch.ones(W), torch.tensor([W]).float()]) / (2 * W)).log()
+        c = (float(log_marginal[0]), float(log_marginal[W]), float(torch.log(torch.tensor([2.0 * W]))[0]))
+        _STTR_CONSTANTS[W] = c
+    return c
+
+
+def _sttr_args(who, attn, phi, ot, iters):
+    """Checks of the three STTR entry points -> phi as a dense [1] tensor (a differentiable view; read on the device)."""
+    if not isinstance(attn, torch.Tensor) or attn.dim() != 4 or attn.shape[2] != attn.shape[3]:
+        raise StxError(f"{who}: attn must be [N, H, W, W], got {tuple(attn.shape) if isinstance(attn, torch.Tensor) else attn!r}")
+    if attn.dtype != torch.float32:
+        raise StxError(f"{who}: attn must be float32, got {attn.dtype}")
+    if not attn.is_contiguous():
+        raise StxError(f"{who}: attn must be a dense contiguous tensor, strides {attn.stride()}")
+    W = attn.shape[3]
+    if not 2 <= W <= STTR_MAX_W:
+        raise StxError(f"{who}: W={W} outside the supported 2..{STTR_MAX_W}")
+    if ot and not (isinstance(iters, int) and 1 <= iters <= STTR_MAX_ITERS):
+        raise StxError(f"{who}: iters={iters!r} outside the supported 1..{STTR_MAX_ITERS}")
+    if not isinstance(phi, torch.Tensor) or phi.numel() != 1 or phi.dtype != torch.float32:
+        raise StxError(f"{who}: phi must be one float32 value on attn's device")
+    phi = phi.reshape(1)
+    _chk(attn, "attn", 4)
+    _chk(phi, "phi")
+    return phi
+
+
+def _sttr_grad(attn, phi):
+    return torch.is_grad_enabled() and (attn.requires_grad or phi.requires_grad)
+
+
+class SttrTransportFn(torch.autograd.Function):
+    """The dense transported (mode 1) or softmax (mode 0) matrix P [N, H, W+1, W+1] on stx_sttr_transport_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, attn, phi, mode, iters):
+        N, H, W, _ = attn.shape
+        M = W + 1
+        P = torch.empty(N, H, M, M, dtype=torch.float32, device=attn.device)
+        us = vs = None
+        if not isinstance(ctx, _NoCtx):
+            shape = (N, H, iters, M) if mode else (N, H, M)
+            us, vs = (torch.empty(shape, dtype=torch.float64, device=attn.device) for _ in range(2))
+        _call("stx_sttr_transport_fwd", _p(attn), _p(phi), mode, iters, *_sttr_constants(W), _p(P), _p(us), _p(vs), N, H, W)
+        ctx.save_for_backward(attn, phi, us, vs)
+        ctx.cfg = (mode, iters)
+        return P
+
+    @staticmethod
+    def backward(ctx, G):
+        attn, phi, us, vs = ctx.saved_tensors
+        mode, iters = ctx.cfg
+        N, H, W, _ = attn.shape
+        g_attn = torch.empty_like(attn)
+        part = torch.empty(N * H, dtype=torch.float64, device=attn.device)
+        g_phi = torch.empty(1, dtype=torch.float32, device=attn.device)
+        _call("stx_sttr_transport_bwd", _p(G.contiguous()), _p(attn), _p(phi), mode, iters, *_sttr_constants(W), _p(us), _p(vs),
+              _p(g_attn), _p(part), _p(g_phi), N, H, W)
+        return g_attn, g_phi, None, None
+
+
+def _sttr_dense(who, attn, phi, mode, iters):
+    phi = _sttr_args(who, attn, phi, mode, iters)
+    if _sttr_grad(attn, phi):
+        return SttrTransportFn.apply(attn, phi, mode, iters)
+    return SttrTransportFn.forward(_NoCtx(), attn, phi, mode, iters)
+
+
+@fp32_region
+def sttr_optimal_transport(attn, phi, iters):
+    """attn [N, H, W, W] (-inf allowed above the diagonal), phi a device scalar -> the transported matrix [N, H, W+1, W+1] after
+    `iters` log-space Sinkhorn iterations with a dustbin row and column (reference `_optimal_transport`); gradients to attn and
+    phi.  2 <= W <= 431, 1 <= iters <= 10."""
+    return _sttr_dense("sttr_optimal_transport", attn, phi, 1, iters)
+
+
+@fp32_region
+def sttr_softmax(attn, phi):
+    """The row softmax of attn with the dustbin row and column, [N, H, W+1, W+1] (reference `_softmax`)."""
+    return _sttr_dense("sttr_softmax", attn, phi, 0, 1)
+
+
+class SttrHeadFn(torch.autograd.Function):
+    """The fused head on stx_sttr_head_fwd / _bwd -> (disp, occ, arg, bin_left, bin_right[, gt_response]), [N, H, W] each; the
+    transported matrix is never written.  Kept for the backward: the 2 * iters scaling vectors (softmax: row max and sum)."""
+
+    @staticmethod
+    def forward(ctx, attn, phi, mode, iters, mask, target):
+        N, H, W, _ = attn.shape
+        M = W + 1
+
+        def new(*shape, dtype=torch.float32):
+            return torch.empty(*shape, dtype=dtype, device=attn.device)
+        disp, occ, norm, bin_l, bin_r = (new(N, H, W) for _ in range(5))
+        arg = new(N, H, W, dtype=torch.int32)
+        gt = new(N, H, W) if target is not None else None
+        us = vs = None
+        if not isinstance(ctx, _NoCtx):
+            shape = (N, H, iters, M) if mode else (N, H, M)
+            us, vs = new(*shape, dtype=torch.float64), new(*shape, dtype=torch.float64)
+            ctx.set_materialize_grads(False)                             # an output the loss does not use: NULL, not zeros
+        _call("stx_sttr_head_fwd", _p(attn), _p(phi), mode, iters, *_sttr_constants(W), _p(mask), _p(target), _p(disp), _p(occ),
+              _p(norm), _p(arg), _p(gt), _p(bin_l), _p(bin_r), _p(us), _p(vs), N, H, W)
+        ctx.save_for_backward(attn, phi, target, disp, norm, arg, us, vs)
+        ctx.cfg = (mode, iters)
+        ctx.mark_non_differentiable(arg)
+        return (disp, occ, arg, bin_l, bin_r) + (() if gt is None else (gt,))
+
+    @staticmethod
+    def backward(ctx, g_disp, g_occ, _g_arg, g_bin_l, g_bin_r, g_gt=None):
+        attn, phi, target, disp, norm, arg, us, vs = ctx.saved_tensors
+        mode, iters = ctx.cfg
+        N, H, W, _ = attn.shape
+        grads = [None if g is None else g.contiguous() for g in (g_disp, g_occ, g_gt, g_bin_l, g_bin_r)]
+        if all(g is None for g in grads):
+            raise StxError("sttr_regress: backward without a gradient for any output")
+        g_attn = torch.empty_like(attn)
+        part = torch.empty(N * H, dtype=torch.float64, device=attn.device)
+        g_phi = torch.empty(1, dtype=torch.float32, device=attn.device)
+        _call("stx_sttr_head_bwd", *(_p(g) for g in grads), _p(attn), _p(phi), mode, iters, *_sttr_constants(W), _p(target),
+              _p(disp), _p(norm), _p(arg), _p(us), _p(vs), _p(g_attn), _p(part), _p(g_phi), N, H, W)
+        return g_attn, g_phi, None, None, None, None
+
+
+@fp32_region
+def sttr_regress(attn, phi, ot=True, iters=10, occ_mask=None, target=None):
+    """STTR's regression head fused (reference RegressionHead.forward up to the upsampling): attn [N, H, W, W], phi a device
+    scalar -> (disp, occ, gt_response, bin_left, bin_right), [N, H, W] each, and the arg-max index as a sixth tensor.
+    ot: optimal transport with `iters` Sinkhorn iterations, else the softmax alternative.  occ_mask (bool [N, H, W]): norm is
+    forced to 1 where it is set; None: where norm < 0.1.  target ([N, H, W], the ground-truth location in low-resolution
+    columns; no gradient): gt_response is the matrix sampled there, None without it.  bin_left / bin_right are the dustbin
+    column and row.  Gradients to attn and phi from any subset of the outputs."""
+    who = "sttr_regress"
+    mode = 1 if ot else 0
+    phi = _sttr_args(who, attn, phi, mode, iters)
+    N, H, W, _ = attn.shape
+    if occ_mask is not None:
+        if tuple(occ_mask.shape) != (N, H, W) or occ_mask.dtype != torch.bool or occ_mask.device != attn.device:
+            raise StxError(f"{who}: occ_mask must be a bool tensor [{N}, {H}, {W}] on attn's device, got {tuple(occ_mask.shape)} "
+                           f"{occ_mask.dtype}")
+        occ_mask = occ_mask.contiguous()
+    if target is not None:
+        if tuple(target.shape) != (N, H, W):
+            raise StxError(f"{who}: target must be [{N}, {H}, {W}], got {tuple(target.shape)}")
+        target = target.detach().contiguous()
+        _chk(target, "target")
+    if _sttr_grad(attn, phi):
+        got = SttrHeadFn.apply(attn, phi, mode, iters if mode else 1, occ_mask, target)
+    else:
+        got = SttrHeadFn.forward(_NoCtx(), attn, phi, mode, iters if mode else 1, occ_mask, target)
+    disp, occ, arg, bin_l, bin_r = got[:5]
+    return disp, occ, (got[5] if target is not None else None), bin_l, bin_r, arg

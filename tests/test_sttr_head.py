@@ -1,0 +1,454 @@
+"""STTR's matching head (reference models/STTR/regression_head.py) on the kernels of csrc/sttr_head.hip: the fused head
+(`ops.sttr_regress`, `RegressionHead.forward`) and the dense pair (`ops.sttr_optimal_transport` / `ops.sttr_softmax`).
+
+* tests/golden/sttr_head.npz holds what the reference's OWN head gives on the seeded cases of tests/golden/sttr_config.py, in fp32
+  and in fp64, and per tensor d_ref = max|fp32 - fp64| > 0 (tests/golden/make_golden_sttr.py).  Tensors of more than WHOLE elements
+  keep d_ref, max|fp64| and a strided subsample of the fp64 tensor.  The generator asserts at every pixel that the arg-max is
+  separated ((top1 - top2) / top1 >= 1e-3), that the window sum stays 1e-4 away from the 0.1 threshold and that the fp32 and fp64
+  runs take the same branch: no pixel is left out of any comparison here.
+* A plain-torch restatement lives in this file and is pinned to the fixture on the CPU first -- in fp64 to 1e-11 (whole tensors or
+  the subsample), in fp32 to 2 x d_ref -- and then serves as the fp64 oracle of the subsampled tensors.
+* The product (emulator build here, gfx950 with `-m gpu`) is compared with fp64: values within VALUE_FACTOR (2) x d_ref, gradients
+  within GRAD_FACTOR (3) x d_ref, floor 2e-7 * max(1, max|want|) where d_ref is zero.  Every element of every tensor is compared
+  and the achieved ratios go to the parity report.
+* g_phi is a scalar per loss; the fixture keeps the g_phi of a record's losses (summed, each output alone) as ONE tensor with one
+  d_ref (sttr_config.layout).  d_ref is a maximum over a tensor so that it measures the reference's fp32 error; of a lone scalar it
+  is the residue of a single rounding (in these cases down to 0.05 ulp of the value: 3.4e-9 on 0.62, 3.4e-10 on 0.063), which only
+  the reference's own bits can meet.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from stereo_toolbox_amd import ops
+from stereo_toolbox_amd.models import STTR
+from tests.backends import be, ptr  # noqa: F401
+from tests.golden.sttr_config import (CASE_VARIANTS, CASES, FORWARD_CASES, FORWARD_KEYS, GPU_ONLY, OUTPUTS, SCALE, VARIANTS, StandInCal,
+                                      forward_inputs, inputs, is_whole, layout, losses, outputs_of, subsample)
+from tests.test_geo_lookup import VALUE_FACTOR, env  # noqa: F401
+from tests.test_models import GRAD_FACTOR, Env
+from tests.test_stereoanywhere import _on, _sync, _within
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sttr_head.npz")
+RECORDS = [(tag, var) for tag in CASES for var in CASE_VARIANTS[tag]]
+NINF = float("-inf")
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(GOLD)
+
+
+def _low(t):
+    return t[..., 1::SCALE, 1::SCALE]
+
+
+def _case_inputs(tag, var):
+    """(attn, phi, occlusion mask or None [N, H, W], full-resolution ground truth or None, loss weights by output)"""
+    ot, use_mask, use_target = VARIANTS[var]
+    x = inputs(tag)
+    return x["attn"], x["phi"], (_low(x["occ_mask"]) if use_mask else None), (x["disp_gt"] if use_target else None), dict(zip(OUTPUTS, x["gws"]))
+
+
+# ------------------------------------------------------------------------------------------ the restatement (plain torch)
+def constants(W):
+    """log mu = log nu and log 2W: fp32 host tensors, in an fp64 run as well"""
+    return (torch.cat([torch.ones(W), torch.tensor([W]).float()]) / (2 * W)).log(), torch.log(torch.tensor([2.0 * W]))
+
+
+def transported(attn, phi, ot, iters):
+    """[N, H, W, W] -> P [N, H, W+1, W+1]"""
+    N, H, W, _ = attn.shape
+    S = torch.cat([torch.cat([attn, phi.expand(N, H, W, 1)], -1), phi.expand(N, H, 1, W + 1)], -2)
+    if not ot:
+        return torch.softmax(S, dim=-1)
+    lm, l2w = constants(W)
+    u = torch.zeros(N, H, W + 1, dtype=attn.dtype)
+    for _ in range(iters):
+        v = lm - torch.logsumexp(S + u.unsqueeze(3), dim=2)
+        u = lm - torch.logsumexp(S + v.unsqueeze(2), dim=3)
+    return (S + u.unsqueeze(3) + v.unsqueeze(2) + l2w).exp()
+
+
+def target_of(disp_gt):
+    """full-resolution ground truth [N, 3H, 3W] -> the right position of every sampled pixel in low-resolution columns"""
+    w = disp_gt.shape[-1]
+    return _low(torch.arange(w, dtype=torch.float32) - disp_gt) / float(SCALE)
+
+
+def regress(P, mask, target):
+    """P [N, H, W+1, W+1] -> the five outputs ('gt' only with a target), the arg-max and where norm was forced.  The steps come in
+    the order of the reference's forward (ground-truth response, regression, dustbins): autograd then adds the gradients that
+    meet in P in the same order, and the fp32 run agrees with the reference's to the last bit or two."""
+    inner = P[..., :-1, :-1]
+    W = inner.shape[-1]
+    out = {}
+    if target is not None:
+        t = target.to(P.dtype).unsqueeze(-1)
+        left, right = torch.floor(t).long().clamp(0, W - 1), torch.ceil(t).long().clamp(0, W - 1)
+        w_right = t - left
+        out["gt"] = (torch.gather(inner, -1, left) * (1 - w_right) + torch.gather(inner, -1, right) * w_right).squeeze(-1)
+    cols = inner.argmax(-1, keepdim=True) + torch.arange(-1, 2)
+    inside = ((cols >= 0) & (cols < W)).to(P.dtype)
+    taps = torch.gather(inner, -1, cols.clamp(0, W - 1)) * inside
+    shift = (torch.arange(W).view(W, 1) - cols).clamp_min(0).to(torch.float32) * inside.float()
+    raw = taps.sum(-1, keepdim=True)
+    forced = mask.unsqueeze(-1) if mask is not None else raw.detach() < 0.1
+    norm = torch.where(forced, torch.ones_like(raw), raw)
+    out["disp"] = (taps / norm * shift).sum(-1)
+    out["occ"] = (1.0 - norm).squeeze(-1)
+    out["bin_l"], out["bin_r"] = P[..., :-1, -1], P[..., -1, :-1]
+    return out, cols[..., 1], forced.squeeze(-1)
+
+
+def _restated(tag, var, dtype):
+    ot = VARIANTS[var][0]
+    iters = CASES[tag][3]
+    attn, phi, mask, disp_gt, gws = _case_inputs(tag, var)
+    target = None if disp_gt is None else target_of(disp_gt.to(dtype))
+    outs = outputs_of(var)
+    res = {}
+    for which in losses(var):
+        a, p = attn.to(dtype).clone().requires_grad_(), phi.to(dtype).clone().requires_grad_()
+        P = transported(a, p, ot, iters)
+        out, _, _ = regress(P, mask, target)
+        sum((out[k] * gws[k].to(dtype)).sum() for k in outs if which in ("all", k)).backward()
+        if which == "all":
+            res.update({k: out[k].detach() for k in outs})
+            res["P"] = P.detach()
+        res["g_attn:" + which], res["g_phi:" + which] = a.grad, p.grad
+    res["g_phi"] = torch.stack([res.pop("g_phi:" + which) for which in losses(var)])
+    return res
+
+
+@functools.lru_cache(maxsize=4)
+def _restated64(tag, var):
+    return _restated(tag, var, torch.float64)
+
+
+def _record(gold, tag, var):
+    """key -> (fp64 whole tensor or None, fp32 whole tensor or None, fp64 subsample or None, d_ref, max|fp64|)"""
+    key = f"{tag}:{var}"
+    f64 = torch.from_numpy(gold[key + ":f64"])
+    f32 = torch.from_numpy(gold[key + ":f32"]) if key + ":f32" in gold else None
+    dref, peak = gold[key + ":dref"], gold[key + ":max"]
+    rec, at64, at32 = {}, 0, 0
+    for n, (k, shape) in enumerate(layout(tag, var)):
+        numel = int(np.prod(shape))
+        if is_whole(shape):
+            rec[k] = (f64[at64:at64 + numel].reshape(shape), f32[at32:at32 + numel].reshape(shape), None, float(dref[n]), float(peak[n]))
+            at64, at32 = at64 + numel, at32 + numel
+        else:
+            sub = subsample(torch.empty(numel)).numel()
+            rec[k] = (None, None, f64[at64:at64 + sub], float(dref[n]), float(peak[n]))
+            at64 += sub
+    assert at64 == f64.numel() and (f32 is None or at32 == f32.numel()), key
+    return rec
+
+
+@pytest.mark.parametrize("tag,var", RECORDS)
+def test_restatement_matches_reference_fixture(gold, tag, var):
+    r64, r32 = _restated64(tag, var), _restated(tag, var, torch.float32)
+    rec = _record(gold, tag, var)
+    assert set(rec) == set(r64)
+    for k, (want64, want32, sub, dref, peak) in rec.items():
+        assert dref > 0 or (not VARIANTS[var][0] and k.endswith("bin_r")), k     # (softmax: the dustbin row is the constant 1 / M)
+        tol = 1e-11 * max(1.0, peak)
+        assert abs(r64[k].abs().max().item() - peak) <= tol, k
+        if want64 is not None:
+            assert r32[k].dtype == torch.float32 and r64[k].shape == want64.shape, k
+            assert (r64[k] - want64).abs().max().item() <= tol, k
+            assert (r32[k] - want32).abs().max().item() <= 2 * dref, k
+        else:
+            got = subsample(r64[k])
+            assert got.shape == sub.shape, k
+            assert (got - sub).abs().max().item() <= tol, k
+            assert (r32[k].double() - r64[k]).abs().max().item() <= 2 * dref, k
+
+
+def _want(gold, tag, var, k):
+    want64, _, _, dref, _ = _record(gold, tag, var)[k]
+    return (want64 if want64 is not None else _restated64(tag, var)[k]), dref
+
+
+# ------------------------------------------------------------------------------------------ the product vs fp64
+def _fused(env, tag, var, which="all"):
+    """ops.sttr_regress with the loss on output `which` -> (outputs by name, arg, g_attn, g_phi)"""
+    ot = VARIANTS[var][0]
+    attn, phi, mask, disp_gt, gws = _case_inputs(tag, var)
+    dev = env.device
+    a, p = attn.to(dev).requires_grad_(), phi.to(dev).requires_grad_()
+    with env.ctx():
+        disp, occ, gt, bin_l, bin_r, arg = ops.sttr_regress(a, p, ot, CASES[tag][3], None if mask is None else mask.to(dev),
+                                                            None if disp_gt is None else target_of(disp_gt).to(dev))
+        out = {"disp": disp, "occ": occ, "gt": gt, "bin_l": bin_l, "bin_r": bin_r}
+        sum((out[k] * gws[k].to(dev)).sum() for k in outputs_of(var) if which in ("all", k)).backward()
+        _sync(env)
+    return out, arg, a.grad, p.grad
+
+
+def _dense(env, tag, var, G=None):
+    ot = VARIANTS[var][0]
+    attn, phi, _, _, _ = _case_inputs(tag, var)
+    a, p = attn.to(env.device).requires_grad_(), phi.to(env.device).requires_grad_()
+    with env.ctx():
+        P = ops.sttr_optimal_transport(a, p, CASES[tag][3]) if ot else ops.sttr_softmax(a, p)
+        if G is not None:
+            (P * G.to(env.device)).sum().backward()
+        _sync(env)
+    return P, a.grad, p.grad
+
+
+@pytest.mark.parametrize("backend,rec", _on(RECORDS, [r for r in RECORDS if r[0] in GPU_ONLY]))
+def test_fused_head_matches_reference_fp64(backend, rec, gold, parity_log):
+    """Every output, g_attn and g_phi of the summed loss and of each output's loss alone."""
+    tag, var = rec
+    env = Env(backend)
+    N, H, W, _ = CASES[tag]
+    outs = outputs_of(var)
+    name = f"sttr {tag} {var}"
+    g_phis = []
+    for which in losses(var):
+        out, arg, g_attn, g_phi = _fused(env, tag, var, which)
+        if which == "all":
+            assert out["gt"] is None or "gt" in outs
+            for k in outs:
+                assert out[k].shape == (N, H, W) and out[k].dtype == torch.float32
+                _within(parity_log, out[k], *_want(gold, tag, var, k), VALUE_FACTOR, f"{name} {k} [{backend}]")
+            want_arg = regress(_restated64(tag, var)["P"], None, None)[1]
+            assert arg.dtype == torch.int32 and torch.equal(arg.cpu().long() & 0xFFFF, want_arg)
+        assert g_attn.shape == (N, H, W, W) and g_phi.shape == ()
+        assert (g_attn.cpu()[torch.isinf(inputs(tag)["attn"])] == 0).all()
+        _within(parity_log, g_attn, *_want(gold, tag, var, "g_attn:" + which), GRAD_FACTOR, f"{name} g_attn:{which} [{backend}]")
+        g_phis.append(g_phi)
+    _within(parity_log, torch.stack(g_phis), *_want(gold, tag, var, "g_phi"), GRAD_FACTOR, f"{name} g_phi [{backend}]")
+
+
+@pytest.mark.parametrize("backend,rec", _on(RECORDS, [r for r in RECORDS if r[0] in GPU_ONLY]))
+def test_dense_pair_matches_reference_fp64(backend, rec, gold, parity_log):
+    """The dense matrix, and -- fed the fp64 gradient of the regression's summed loss with respect to P -- the same g_attn and
+    g_phi as the fused head's."""
+    tag, var = rec
+    env = Env(backend)
+    _, _, mask, disp_gt, gws = _case_inputs(tag, var)
+    P64 = _restated64(tag, var)["P"].clone().requires_grad_()
+    out, _, _ = regress(P64, mask, None if disp_gt is None else target_of(disp_gt.double()))
+    sum((out[k] * gws[k].double()).sum() for k in outputs_of(var)).backward()
+    P, g_attn, g_phi = _dense(env, tag, var, P64.grad.float())
+    name = f"sttr dense {tag} {var}"
+    _within(parity_log, P, *_want(gold, tag, var, "P"), VALUE_FACTOR, f"{name} P [{backend}]")
+    _within(parity_log, g_attn, *_want(gold, tag, var, "g_attn:all"), GRAD_FACTOR, f"{name} g_attn [{backend}]")
+    want_phi, dref_phi = _want(gold, tag, var, "g_phi")
+    _within(parity_log, g_phi, want_phi[0], dref_phi, GRAD_FACTOR, f"{name} g_phi [{backend}]")
+
+
+@pytest.mark.parametrize("backend,tag", _on(["w17", "w320"], ["w320"]))
+def test_outputs_are_bitwise_reproducible(backend, tag):
+    """Every output of the four kernels, twice (tests/test_hygiene._twice in spirit: fresh outputs, bit for bit)."""
+    env = Env(backend)
+    for var in ("ot", "sm_mask"):
+        a, b = _fused(env, tag, var), _fused(env, tag, var)
+        assert all(torch.equal(a[0][k], b[0][k]) for k in outputs_of(var)) and torch.equal(a[1], b[1])
+        assert torch.equal(a[2], b[2]) and torch.equal(a[3], b[3]) and a[2].abs().max().item() > 0
+        M = CASES[tag][2] + 1
+        G = torch.cos(torch.arange(M * M, dtype=torch.float32)).view(M, M)
+        a, b = _dense(env, tag, var, G), _dense(env, tag, var, G)
+        assert all(torch.equal(x, y) for x, y in zip(a, b)) and a[1].abs().max().item() > 0
+
+
+# ------------------------------------------------------------------------------------------ finite differences (emulator)
+def _fd_attn(W=9, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    attn = 2.0 * torch.randn(1, 2, W, W, generator=g)
+    d = torch.randint(0, 3, (1, 2, W, 1), generator=g)
+    i, j = torch.arange(W).view(1, 1, W, 1), torch.arange(W).view(1, 1, 1, W)
+    attn = attn + 8.0 * (j == (i - d).clamp_min(0))
+    return attn.masked_fill(j > i, NINF), (j <= i).float().expand(1, 2, W, W)
+
+
+@pytest.mark.parametrize("ot", [True, False])
+def test_finite_difference_gradients(ot):
+    """<gradient, direction> against the central difference, for attn (finite entries only) and phi, through the fused head and
+    the dense pair.  The step is small enough that no arg-max and no forced norm changes, which is asserted."""
+    from tests.emu_util import emu_product_path
+    attn, finite = _fd_attn()
+    phi = torch.tensor(0.3)
+    target = torch.rand(1, 2, 9, generator=torch.Generator().manual_seed(5)) * 8.0
+    g = torch.Generator().manual_seed(1)
+    gy = [torch.randn(1, 2, 9, generator=g) for _ in range(5)]
+    gp = torch.randn(1, 2, 10, 10, generator=g)
+    va, vp, eps = torch.randn(attn.shape, generator=g) * finite, 1.0, 2e-3
+
+    def fused(a, p):
+        disp, occ, gt, bl, br, arg = ops.sttr_regress(a, p, ot, 10, None, target)
+        return sum((o * w).sum() for o, w in zip((disp, occ, gt, bl, br), gy)), arg
+
+    def dense(a, p):
+        P = ops.sttr_optimal_transport(a, p, 10) if ot else ops.sttr_softmax(a, p)
+        return (P * gp).sum(), None
+
+    with emu_product_path():
+        for fn in (fused, dense):
+            a, p = attn.clone().requires_grad_(), phi.clone().requires_grad_()
+            loss, arg = fn(a, p)
+            loss.backward()
+            for da, dp, an in ((va, 0.0, (a.grad[finite > 0] * va[finite > 0]).double().sum().item()), (0.0, vp, p.grad.item() * vp)):
+                with torch.no_grad():
+                    up, arg_up = fn(attn + eps * da, phi + eps * dp)
+                    dn, arg_dn = fn(attn - eps * da, phi - eps * dp)
+                if arg is not None:
+                    assert torch.equal(arg, arg_up) and torch.equal(arg, arg_dn), "the step crossed an arg-max or the 0.1 threshold"
+                fd = (up.double().item() - dn.double().item()) / (2 * eps)
+                assert abs(an - fd) <= 3e-2 * max(abs(an), abs(fd), 1e-3), (fn.__name__, an, fd)
+
+
+# ------------------------------------------------------------------------------------------ the module
+def _head(name, device):
+    tag, ot, mask, gt, down, cal = FORWARD_CASES[name]
+    head = STTR.RegressionHead(StandInCal() if cal else None, ot)
+    with torch.no_grad():
+        head.phi.copy_(inputs(tag)["phi"])
+    f = {k: (None if v is None else v.to(device)) for k, v in forward_inputs(name).items()}
+    x = STTR.NestedTensor(f["left"], f["right"], disp=f["disp"], sampled_cols=f["sampled_cols"], sampled_rows=f["sampled_rows"],
+                          occ_mask=f["occ_mask"], occ_mask_right=f["occ_mask_right"])
+    return head.to(device), f["attn"], x
+
+
+@pytest.mark.parametrize("name", list(FORWARD_CASES))
+def test_forward_matches_reference_fp64(env, gold, parity_log, name):  # noqa: F811
+    """The whole dictionary: boolean-indexed dustbin responses, the downsampled path with a stand-in cal and with cal=None."""
+    tag, ot, mask, gt, down, cal = FORWARD_CASES[name]
+    head, attn, x = _head(name, env.device)
+    with env.ctx(), torch.no_grad():
+        out = head(attn, x)
+        _sync(env)
+    assert set(out) == set(FORWARD_KEYS if down else FORWARD_KEYS[:5])
+    for k in out:
+        key = f"fwd:{name}:{k}"
+        if key + ":f64" not in gold:
+            assert out[k] is None and (k == "gt_response" and not gt or k.startswith("gt_response_occ") and not mask), k
+            continue
+        _within(parity_log, out[k], torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), VALUE_FACTOR,
+                f"sttr forward {name} {k} [{env.name}]")
+
+
+def test_dense_methods_give_the_fused_outputs(env, gold, parity_log):  # noqa: F811
+    """The reference's steps one by one on the dense pair: the same tensors as the fused head, within the same bounds."""
+    tag, var = "w17", "ot_mask"
+    attn, phi, mask, _, _ = _case_inputs(tag, var)
+    x = inputs(tag)
+    head = STTR.RegressionHead(None, True)
+    with torch.no_grad():
+        head.phi.copy_(phi)
+    head = head.to(env.device)
+    with env.ctx(), torch.no_grad():
+        P = head._optimal_transport(attn.to(env.device), CASES[tag][3])
+        disp, norm = head._compute_low_res_disp(head._compute_unscaled_pos_shift(CASES[tag][2], env.device), P[..., :-1, :-1],
+                                                mask.to(env.device))
+        occ = head._compute_low_res_occ(norm)
+        gt, _ = head._compute_gt_location(float(SCALE), x["sampled_cols"].to(env.device), x["sampled_rows"].to(env.device),
+                                          P[..., :-1, :-1], x["disp_gt"].to(env.device))
+        assert torch.equal(head._softmax(attn.to(env.device)).sum(-1).cpu().round(decimals=4), torch.ones(1, 3, 18))
+        _sync(env)
+    _within(parity_log, disp, *_want(gold, tag, var, "disp"), VALUE_FACTOR, f"sttr steps disp [{env.name}]")
+    _within(parity_log, occ, *_want(gold, tag, var, "occ"), VALUE_FACTOR, f"sttr steps occ [{env.name}]")
+    _within(parity_log, gt, *_want(gold, tag, "ot", "gt"), VALUE_FACTOR, f"sttr steps gt [{env.name}]")
+    S = torch.cat([torch.cat([attn, phi.expand(1, 3, 17, 1)], -1), phi.expand(1, 3, 1, 18)], -2)
+    lm, l2w = constants(17)
+    assert (((head._sinkhorn(S.double(), lm.expand(1, 3, 18), lm.expand(1, 3, 18), CASES[tag][3]) + l2w).exp() - _restated64(tag, var)["P"]).abs().max().item()) < 1e-12
+
+
+def test_state_dict_keys():
+    assert list(STTR.RegressionHead(None).state_dict()) == ["phi"]
+    assert list(STTR.RegressionHead(StandInCal(), ot=False).state_dict()) == ["phi", "cal.weight"]
+
+
+def test_fully_masked_upper_triangle_is_finite(env):  # noqa: F811
+    """Nothing but -inf above the diagonal (row 0: one finite entry and the dustbin): finite outputs, exact zeros in the gradient
+    at the masked entries, no NaN anywhere -- both modes."""
+    W = 21
+    attn = torch.zeros(1, 2, W, W).masked_fill(torch.arange(W).view(1, W) > torch.arange(W).view(W, 1), NINF)
+    target = torch.full((1, 2, W), 3.5)
+    for ot in (True, False):
+        a, p = attn.to(env.device).requires_grad_(), torch.tensor(0.3, device=env.device).requires_grad_()
+        with env.ctx():
+            outs = ops.sttr_regress(a, p, ot, 10, None, target.to(env.device))
+            sum(o.sum() for o in outs[:5]).backward()
+            P = ops.sttr_optimal_transport(a, p, 10) if ot else ops.sttr_softmax(a, p)
+            _sync(env)
+        assert all(torch.isfinite(o).all() for o in outs[:5]) and torch.isfinite(P).all()
+        assert (P.cpu()[..., :W, :W][torch.isinf(attn)] == 0).all()
+        g = a.grad.cpu()
+        assert torch.isfinite(g).all() and torch.isfinite(p.grad).all() and (g[torch.isinf(attn)] == 0).all() and g.abs().max() > 0
+
+
+# ------------------------------------------------------------------------------------------ refusals
+def test_cpu_tensors_are_refused():
+    attn = inputs("w17")["attn"]
+    for call in (lambda: ops.sttr_regress(attn, torch.tensor(0.3)), lambda: ops.sttr_optimal_transport(attn, torch.tensor(0.3), 10),
+                 lambda: ops.sttr_softmax(attn, torch.tensor(0.3))):
+        with pytest.raises(ops.StxError, match="ROCm device"):
+            call()
+
+
+def test_unsupported_arguments_are_refused(env):  # noqa: F811
+    dev = env.device
+    attn, phi = inputs("w17")["attn"].to(dev), torch.tensor(0.3, device=dev)
+    with env.ctx():
+        with pytest.raises(ops.StxError, match="outside the supported 2.."):
+            ops.sttr_regress(torch.zeros(1, 1, ops.STTR_MAX_W + 1, ops.STTR_MAX_W + 1, device=dev), phi)
+        with pytest.raises(ops.StxError, match="outside the supported 2.."):
+            ops.sttr_softmax(torch.zeros(1, 1, 1, 1, device=dev), phi)
+        for iters in (0, ops.STTR_MAX_ITERS + 1):
+            with pytest.raises(ops.StxError, match="iters"):
+                ops.sttr_optimal_transport(attn, phi, iters)
+            with pytest.raises(ops.StxError, match="iters"):
+                ops.sttr_regress(attn, phi, True, iters)
+        with pytest.raises(ops.StxError, match="contiguous"):
+            ops.sttr_regress(attn.transpose(2, 3), phi)
+        with pytest.raises(ops.StxError, match="float32"):
+            ops.sttr_optimal_transport(attn.double(), phi, 10)
+        with pytest.raises(ops.StxError, match=r"\[N, H, W, W\]"):
+            ops.sttr_softmax(attn[..., :16], phi)
+        with pytest.raises(ops.StxError, match="occ_mask"):
+            ops.sttr_regress(attn, phi, occ_mask=torch.zeros(1, 3, 17, device=dev))
+        with pytest.raises(ops.StxError, match="target"):
+            ops.sttr_regress(attn, phi, target=torch.zeros(1, 3, 16, device=dev))
+        with pytest.raises(ops.StxError, match="phi"):
+            ops.sttr_regress(attn, torch.zeros(2, device=dev))
+        assert ops.sttr_regress(attn, phi, False, 0)[0].shape == (1, 3, 17)        # softmax: iters unused
+
+
+def test_c_entry_points_refuse_without_launching(be):  # noqa: F811
+    """The C-ABI returns an error -- and writes nothing -- for a width past the limit, iters 0 and 11, a bad mode, no gradient at
+    all, a lone target / us, and the gradient of gt_response without the target."""
+    W = 8
+    attn, phi = be.dev(torch.zeros(1, 1, W, W)), be.dev(torch.zeros(1))
+    o = [be.empty(W) for _ in range(7)]
+    arg = be.empty(W, dtype=torch.int32)
+    us, vs = be.empty(10 * (W + 1), dtype=torch.float64), be.empty(10 * (W + 1), dtype=torch.float64)
+    P, part = be.empty((W + 1) ** 2), be.empty(2, dtype=torch.float64)
+    c = (-2.7, -0.69, 2.7)
+
+    def fwd(mode=1, iters=10, target=None, gt=None, us_=us, vs_=vs, W_=W):
+        return ("stx_sttr_head_fwd", (ptr(attn), ptr(phi), mode, iters, *c, None, target, ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(arg), gt,
+                                      ptr(o[4]), ptr(o[5]), us_, vs_, 1, 1, W_))
+
+    def bwd(grads, target=None, iters=10):
+        return ("stx_sttr_head_bwd", (*grads, ptr(attn), ptr(phi), 1, iters, *c, target, ptr(o[0]), ptr(o[2]), ptr(arg), ptr(us), ptr(vs),
+                                      ptr(P), ptr(part), ptr(o[6]), 1, 1, W))
+    bad = [fwd(W_=512), fwd(W_=1), fwd(iters=0), fwd(iters=11), fwd(mode=2), fwd(target=ptr(o[3])), fwd(us_=None),
+           bwd((None,) * 5), bwd((None, None, ptr(o[3]), None, None)), bwd((ptr(o[3]), None, None, None, None), iters=11),
+           ("stx_sttr_transport_fwd", (ptr(attn), ptr(phi), 1, 0, *c, ptr(P), None, None, 1, 1, W)),
+           ("stx_sttr_transport_fwd", (ptr(attn), ptr(phi), 1, 10, *c, ptr(P), None, None, 1, 1, 512)),
+           ("stx_sttr_transport_bwd", (None, ptr(attn), ptr(phi), 1, 10, *c, ptr(us), ptr(vs), ptr(P), ptr(part), ptr(o[6]), 1, 1, W)),
+           ("stx_sttr_transport_bwd", (ptr(P), ptr(attn), ptr(phi), 1, 11, *c, ptr(us), ptr(vs), ptr(P), ptr(part), ptr(o[6]), 1, 1, W))]
+    for name, args in bad:
+        with pytest.raises(ops.StxError):
+            be.call(name, *args)
+    if be.name == "hip":
+        torch.cuda.synchronize()
+    assert all(torch.isnan(t).all() for t in o + [us, vs, P, part]) and (arg == 0).all()
