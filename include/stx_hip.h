@@ -490,6 +490,22 @@ int stx_sttr_transport_bwd(const float* G, const float* attn, const float* phi, 
                            float log_2w, const double* us, const double* vs, float* g_attn, double* phi_partials, float* g_phi, int N,
                            int H, int W, void* stream);
 
+/* ---- sttr_attention.hip: STTR's attention with relative positional encoding (models/STTR/attention.py), the core between the
+ * q/k/v projection and the output projection.  q (already scaled), k, v, o and their gradients [W][B][E][16] -- the memory a
+ * linear layer on [W][B][C] leaves; Qr, Kr and their gradients [2W-1][E][16], or all NULL (no positional terms).
+ *   S[b][e][w][v] = q[w].k[v] + q[w].Kr[r] + k[v].Qr[r], r = W-1-w+v; causal != 0: -inf where v > w; o = softmax_v(S) v.
+ * Limits: head_dim == 16, 2 <= W <= 431, E <= 8, B <= 65535, fp32.  No float atomics, bitwise reproducible.
+ * stx_sttr_attn_fwd: raw (NULL or [B][W][W]) = sum_e S in head order, -inf where masked; avg (NULL or [B][W][W]) = mean_e
+ *   softmax(S); stats (NULL or [2][B][E][W]) = row max, then row sum: what the backward needs besides o.
+ * stx_sttr_attn_bwd: dO or dRaw may be NULL (not both); entries of dRaw at masked positions contribute exactly 0.  nb = the
+ *   number of chunks the rows b are split into for the table gradients (1 .. B); scratch holds B * E * W floats and, with
+ *   tables, nb * E * W16 * 2 * (W16 + 1) * 256 more, W16 = ceil(W / 16); scratch_floats is its size and is checked. */
+int stx_sttr_attn_fwd(const float* q, const float* k, const float* v, const float* Qr, const float* Kr, int causal, float* o,
+                      float* raw, float* avg, float* stats, int W, int B, int E, int head_dim, void* stream);
+int stx_sttr_attn_bwd(const float* dO, const float* dRaw, const float* q, const float* k, const float* v, const float* Qr,
+                      const float* Kr, const float* o, const float* stats, int causal, float* dq, float* dk, float* dv, float* dQr,
+                      float* dKr, float* scratch, long long scratch_floats, int nb, int W, int B, int E, int head_dim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,9 @@ SIGNATURES = {
     "stx_sttr_head_bwd": [_P] * 7 + [_I, _I, _F, _F, _F] + [_P] * 9 + [_I, _I, _I, _P],
     "stx_sttr_transport_fwd": [_P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _I, _I, _I, _P],
     "stx_sttr_transport_bwd": [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    # sttr_attention.hip
+    "stx_sttr_attn_fwd": [_P] * 5 + [_I] + [_P] * 4 + [_I, _I, _I, _I, _P],
+    "stx_sttr_attn_bwd": [_P] * 9 + [_I] + [_P] * 6 + [_L, _I, _I, _I, _I, _I, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

@@ -11,7 +11,7 @@ from . import FoundationStereo  # noqa: F401  (normalised initial volume only)
 from . import RAFTStereo  # noqa: F401  (correlation blocks only)
 from . import DEFOMStereo  # noqa: F401  (correlation block only)
 from . import StereoAnywhere  # noqa: F401  (volume-in correlation block and volume estimators only)
-from . import STTR  # noqa: F401  (regression head only)
+from . import STTR  # noqa: F401  (transformer and regression head)
 
 
 def load_checkpoint_flexible(model, checkpoint_path, state_dict_key=None):

@@ -2448,3 +2448,109 @@ def sttr_regress(attn, phi, ot=True, iters=10, occ_mask=None, target=None):
         got = SttrHeadFn.forward(_NoCtx(), attn, phi, mode, iters if mode else 1, occ_mask, target)
     disp, occ, arg, bin_l, bin_r = got[:5]
     return disp, occ, (got[5] if target is not None else None), bin_l, bin_r, arg
+
+
+# --------------------------------------------------------------------------------------- STTR attention with relative positions
+STTR_ATTN_HEAD_DIM = 16                                                  # csrc/sttr_attention.hip SA_HD
+STTR_ATTN_MAX_HEADS = 8                                                  # ... SA_MAX_E
+
+
+def _sttr_attn_chunks(W, B, E):
+    """Into how many chunks the table-gradient kernel splits the rows b: about 2048 waves, one per (chunk, head, 16 queries) --
+    two per SIMD of an MI355X; measured at 192 x 320: 1024 waves 7.0 ms per backward, 2048 6.0 ms, 4096 and more no faster."""
+    per = E * ((W + 15) // 16)
+    return max(1, min(B, (2048 + per - 1) // per))
+
+
+def sttr_attn_scratch_floats(W, B, E, tables=True):
+    """Floats of scratch one backward call takes: the row sums dO . o and the partial windows of dQr / dKr."""
+    W16 = (W + 15) // 16
+    return B * E * W + (_sttr_attn_chunks(W, B, E) * E * W16 * 2 * (W16 + 1) * 256 if tables else 0)
+
+
+def _sttr_attn_dense(who, name, t):
+    if t.dtype != torch.float32:
+        raise StxError(f"{who}: {name} must be float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise StxError(f"{who}: {name} must be a dense contiguous tensor, strides {t.stride()}")
+
+
+class SttrRelAttentionFn(torch.autograd.Function):
+    """stx_sttr_attn_fwd / _bwd.  Kept for the backward: the inputs, o and the row max / row sum [2, B, E, W]."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_r, k_r, causal, need_raw, need_avg):
+        W, B, E, D = q.shape
+        o = torch.empty_like(q)
+        raw = torch.empty(B, W, W, dtype=torch.float32, device=q.device) if need_raw else None
+        avg = torch.empty(B, W, W, dtype=torch.float32, device=q.device) if need_avg else None
+        stats = None
+        if not isinstance(ctx, _NoCtx):
+            stats = torch.empty(2, B, E, W, dtype=torch.float32, device=q.device)
+            ctx.set_materialize_grads(False)
+        _call("stx_sttr_attn_fwd", _p(q), _p(k), _p(v), _p(q_r), _p(k_r), int(causal), _p(o), _p(raw), _p(avg), _p(stats), W, B, E, D)
+        ctx.save_for_backward(q, k, v, q_r, k_r, o, stats)
+        ctx.causal = causal
+        if avg is not None:
+            ctx.mark_non_differentiable(avg)
+        return o, raw, avg
+
+    @staticmethod
+    def backward(ctx, g_o, g_raw, _g_avg):
+        q, k, v, q_r, k_r, o, stats = ctx.saved_tensors
+        W, B, E, D = q.shape
+        if g_o is None and g_raw is None:
+            raise StxError("sttr_rel_attention: backward without a gradient for o or raw")
+        g_o = None if g_o is None else g_o.contiguous()
+        g_raw = None if g_raw is None else g_raw.contiguous()
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dqr = dkr = None
+        if q_r is not None:
+            dqr, dkr = torch.empty_like(q_r), torch.empty_like(k_r)
+        n = sttr_attn_scratch_floats(W, B, E, q_r is not None)
+        scratch = torch.empty(n, dtype=torch.float32, device=q.device)
+        _call("stx_sttr_attn_bwd", _p(g_o), _p(g_raw), _p(q), _p(k), _p(v), _p(q_r), _p(k_r), _p(o), _p(stats), int(ctx.causal),
+              _p(dq), _p(dk), _p(dv), _p(dqr), _p(dkr), _p(scratch), n, _sttr_attn_chunks(W, B, E), W, B, E, D)
+        return dq, dk, dv, dqr, dkr, None, None, None
+
+
+@fp32_region
+def sttr_rel_attention(q, k, v, q_r=None, k_r=None, causal=False, need_raw=False, need_avg=False):
+    """The core of STTR's `MultiheadAttentionRelative` (reference models/STTR/attention.py:98-137) between the projections.
+    q (already scaled), k, v: [W, B, E, 16] dense fp32 -- a view of what a linear layer on [W, B, C] leaves; q_r (scaled) and
+    k_r: the PROJECTED relative table [2W-1, E, 16], both or neither.  The scores are
+        S[b, e, w, v] = q[w].k[v] + q[w].k_r[W-1-w+v] + k[v].q_r[W-1-w+v]
+    which is the reference's three einsums for its pos_indexes[w, v] = (W-1-w) + v; `causal` adds its upper-triangular -inf mask.
+    -> (o [W, B, E, 16] = softmax_v(S) v, raw [B, W, W] = sum_e S or None, avg [B, W, W] = mean_e softmax(S) or None).
+    Gradients reach q, k, v, q_r and k_r through o and raw; avg is a debugging output and is NOT differentiable.
+    2 <= W <= 431, at most 8 heads, head dim 16 only."""
+    who = "sttr_rel_attention"
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise StxError(f"{who}: {name} must be [W, B, E, 16], got {tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
+        _sttr_attn_dense(who, name, t)
+        _chk(t, f"{who}: {name}", 4)
+    W, B, E, D = q.shape
+    if D != STTR_ATTN_HEAD_DIM:
+        raise StxError(f"{who}: head dim {D} is not supported, only {STTR_ATTN_HEAD_DIM}")
+    if tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape):
+        raise StxError(f"{who}: q, k and v must have one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    if not 2 <= W <= STTR_MAX_W:
+        raise StxError(f"{who}: W={W} outside the supported 2..{STTR_MAX_W}")
+    if not 1 <= E <= STTR_ATTN_MAX_HEADS:
+        raise StxError(f"{who}: {E} heads outside the supported 1..{STTR_ATTN_MAX_HEADS}")
+    if B < 1 or B > 65535:
+        raise StxError(f"{who}: B={B} rows outside the supported 1..65535")
+    if (q_r is None) != (k_r is None):
+        raise StxError(f"{who}: q_r and k_r go together (the projected relative table, or neither)")
+    for name, t in (("q_r", q_r), ("k_r", k_r)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (2 * W - 1, E, D):
+            raise StxError(f"{who}: {name} must be [2W-1, E, 16] = [{2 * W - 1}, {E}, {D}], got {tuple(t.shape)}")
+        _sttr_attn_dense(who, name, t)
+        _chk(t, f"{who}: {name}", 3)
+    args = (q, k, v, q_r, k_r, bool(causal), bool(need_raw), bool(need_avg))
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in args[:5]):
+        return SttrRelAttentionFn.apply(*args)
+    return SttrRelAttentionFn.forward(_NoCtx(), *args)
