@@ -506,6 +506,40 @@ int stx_sttr_attn_bwd(const float* dO, const float* dRaw, const float* q, const 
                       const float* Kr, const float* o, const float* stats, int causal, float* dq, float* dk, float* dv, float* dQr,
                       float* dKr, float* scratch, long long scratch_floats, int nb, int W, int B, int E, int head_dim, void* stream);
 
+/* ---- convex_upsample.hip: convex upsampling with the soft-max fused, and the trainer's sequence loss; fp32 tensors -------------
+ * RAFT layout (upsample_flow of RAFTStereo / DEFOMStereo, convex_upflow of StereoAnywhere, upsample_disp of SelectiveRAFT):
+ *   flow [N][D][H][W], mask [N][9 f f][H][W] (logits, channel (t f + j) f + i), out [N][D][f H][f W]:
+ *   out[n][d][f y + j][f x + i] = sum_t softmax_t(mask[n][t][j][i][y][x]) * scale * flow[n][d][y + t/3 - 1][x + t%3 - 1], zero
+ *   outside.  f in {2, 4, 8}, mask_channels == 9 f f, D >= 1; anything else is an error and nothing is launched.
+ * Pixel layout (IGEV family): disp_low [B][1][h][w], logits [B][9][4h][4w], out [B][4h][4w]:
+ *   out[b][Y][X] = sum_t softmax_t(logits[b][t][Y][X]) * scale * disp_low[b][Y/4 + t/3 - 1][X/4 + t%3 - 1].
+ * The soft-max (maximum subtracted), the nine-term sums and the gradients are formed in double.  The backward re-forms the
+ * soft-max from the logits: nothing but the two inputs is needed.  gflow / gmask (gdisp / glogits): either may be NULL.  The
+ * flow's gradient needs a workspace of stx_convex_upsample_bwd_workspace_floats(N, D, H, W) floats (pixel layout: (B, 1, h, w)),
+ * 8-byte aligned.  out, g and the pixel layout's logits / glogits must be 16-byte aligned.  No atomics, bitwise reproducible. */
+int stx_convex_upsample_fwd(const float* flow, const float* mask, float* out, int N, int D, int H, int W, int mask_channels, int f,
+                            float scale, void* stream);
+long long stx_convex_upsample_bwd_workspace_floats(int N, int D, int H, int W);
+int stx_convex_upsample_bwd(const float* g, const float* flow, const float* mask, float* gflow, float* gmask, float* workspace, int N,
+                            int D, int H, int W, int mask_channels, int f, float scale, void* stream);
+int stx_softmax_context_upsample_fwd(const float* disp_low, const float* logits, float* out, int B, int h, int w, float scale,
+                                     void* stream);
+int stx_softmax_context_upsample_bwd(const float* g, const float* disp_low, const float* logits, float* gdisp, float* glogits,
+                                     float* workspace, int B, int h, int w, float scale, void* stream);
+/* Sequence loss (trainer/trainer_torchrun.py:272-284): loss[0] = sum_k weights[k] * (sum_valid smooth_l1(preds[k] - gt)) /
+ *   max(1, #valid), valid = (gt > 0) & (gt < maxdisp - 1), beta = 1; a NaN / inf gt is excluded, never multiplied.  preds is a HOST
+ *   array of K device pointers (n floats each), weights a HOST array of K doubles: both are packed by value into the kernel's
+ *   arguments.  1 <= K <= stx_sequence_loss_max_predictions(), n < 2^31.  count[0] (device) receives #valid; workspace =
+ *   stx_sequence_loss_workspace_floats(n) floats, 8-byte aligned.  No host sync, no float atomics.
+ * stx_sequence_loss_bwd: gpreds (HOST array of K device pointers, entries may be NULL) receive
+ *   weights[k] * clamp(preds[k] - gt, -1, 1) * gloss[0] / max(1, count[0]), exactly 0 at excluded pixels. */
+int stx_sequence_loss_max_predictions(void);
+long long stx_sequence_loss_workspace_floats(long long n);
+int stx_sequence_loss_fwd(const float* const* preds, const double* weights, int K, const float* gt, float maxdisp, float* loss,
+                          int* count, float* workspace, long long n, void* stream);
+int stx_sequence_loss_bwd(const float* gloss, const float* const* preds, const double* weights, int K, const float* gt, float maxdisp,
+                          const int* count, float* const* gpreds, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,16 @@ SIGNATURES = {
     # sttr_attention.hip
     "stx_sttr_attn_fwd": [_P] * 5 + [_I] + [_P] * 4 + [_I, _I, _I, _I, _P],
     "stx_sttr_attn_bwd": [_P] * 9 + [_I] + [_P] * 6 + [_L, _I, _I, _I, _I, _I, _P],
+    # convex_upsample.hip
+    "stx_convex_upsample_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "stx_convex_upsample_bwd_workspace_floats": [_I, _I, _I, _I],
+    "stx_convex_upsample_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "stx_softmax_context_upsample_fwd": [_P, _P, _P, _I, _I, _I, _F, _P],
+    "stx_softmax_context_upsample_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "stx_sequence_loss_max_predictions": [],
+    "stx_sequence_loss_workspace_floats": [_L],
+    "stx_sequence_loss_fwd": [_P, _P, _I, _P, _F, _P, _P, _P, _L, _P],
+    "stx_sequence_loss_bwd": [_P, _P, _P, _I, _P, _F, _P, _P, _L, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

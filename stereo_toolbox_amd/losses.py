@@ -32,3 +32,20 @@ def masked_smooth_l1_multi(preds, gt, maxdisp, weights=GWCNET_WEIGHTS):
         gt_safe = torch.where(mask, gt, p.detach())  # excluded pixels: zero residual, zero gradient, never NaN
         loss = loss + w * torch.where(mask, F.smooth_l1_loss(p, gt_safe, reduction="none"), zero).sum() * inv
     return loss
+
+
+def sequence_loss_weights(n_predictions, loss_gamma=0.9):
+    """The trainer's weights (trainer_torchrun.py:281-283): 1 for the initial disparity, then gamma_adj ^ (n - i - 1) for prediction
+    i, gamma_adj = loss_gamma ^ (15 / (n - 1)).  n < 2 raises: the reference divides by zero there."""
+    if n_predictions < 2:
+        raise ValueError(f"sequence_loss_weights: {n_predictions} predictions -- the trainer's 15 / (n - 1) needs at least two")
+    adjusted = loss_gamma ** (15 / (n_predictions - 1))
+    return [1.0] + [adjusted ** (n_predictions - i - 1) for i in range(n_predictions)]
+
+
+def sequence_loss(init_disp, disp_preds, gt, maxdisp, loss_gamma=0.9):
+    """The loss of `Trainer._train_iteration` (trainer_torchrun.py:272-284) for the iterative models: masked smooth-L1 of the
+    initial disparity plus the gamma-weighted sum over `disp_preds`, all predictions in one launch (ops.sequence_loss)."""
+    from . import ops
+    disp_preds = list(disp_preds)
+    return ops.sequence_loss([init_disp] + disp_preds, gt, maxdisp, sequence_loss_weights(len(disp_preds), loss_gamma))

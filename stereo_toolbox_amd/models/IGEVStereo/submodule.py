@@ -56,3 +56,10 @@ def context_upsample(disp_low, up_weights):
     the up_weights-weighted sum of the 3x3 low-resolution neighbourhood of its cell (zero padding); one fused kernel forward,
     two backward (stx_context_upsample_fwd / _bwd), no unfolded or nearest-upsampled temporary."""
     return ops.context_upsample(disp_low, up_weights)
+
+
+def upsample_disp_from_logits(disp, spx_logits):
+    """The two lines `spx_pred = F.softmax(spx_pred, 1)`, `context_upsample(disp * 4., spx_pred)` of igev_stereo.py:158-166 (and of
+    MonSter, FoundationStereo, Selective-IGEV) in one kernel that takes the LOGITS of the `spx` head: disp [B,1,h,w], spx_logits
+    [B,9,4h,4w] -> [B,4h,4w].  The full-resolution soft-max pass and its saved output are gone; the backward re-forms it."""
+    return ops.softmax_context_upsample(disp, spx_logits, 4.0)

@@ -1,1 +1,2 @@
 from .corr import CorrBlock1D, CorrBlockFast1D, PytorchAlternateCorrBlock1D  # noqa: F401
+from .upsample import upsample_flow  # noqa: F401

@@ -40,3 +40,9 @@ def estimate_right_confidence(corr_volume, logsumexp_eps=1e-3):
 def truncate_corr_volume_v2(disp_left, conf_left, conf_th=0.5, attenuation_gain=0.1):
     """[B, 1, H, W] x 2 -> the mask volume [B, 1, H, W, W] (utils.py:216-238); conf_th=None uses conf_left as it is."""
     return ops.truncate_mask(disp_left, conf_left, conf_th, attenuation_gain)
+
+
+def convex_upflow(flow, mask, n_downsample=2, use_scale_factor=True):
+    """reference StereoAnywhere/utils/utils.py:97-110 on the fused kernel of csrc/convex_upsample.hip: flow [N,D,H,W], mask
+    [N,9*4^n,H,W] (logits) -> [N,D,2^n H,2^n W]."""
+    return ops.convex_upsample(flow, mask, n_downsample=n_downsample, use_scale_factor=use_scale_factor)

@@ -2068,6 +2068,182 @@ def context_upsample(disp_low, up_weights):
     return ContextUpsampleFn.forward(_NoCtx(), disp_low, up_weights)
 
 
+# --------------------------------------------------------------------------------------- convex upsampling from logits, sequence loss
+CONVEX_FACTORS = (2, 4, 8)                                               # csrc/convex_upsample.hip
+
+
+def _aligned16(t):
+    """The kernels move whole output rows as 16-byte vectors: a dense tensor that starts inside a larger storage is copied."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+class ConvexUpsampleFn(torch.autograd.Function):
+    """upsample_flow / convex_upflow / upsample_disp (RAFTStereo/raft_stereo.py:81-93, StereoAnywhere/utils/utils.py:97-110,
+    SelectiveRAFT/raft.py:72-84) on stx_convex_upsample_fwd / _bwd.  Saves the two inputs only: the backward re-forms the soft-max."""
+
+    @staticmethod
+    def forward(ctx, flow, mask, f, scale):
+        N, D, H, W = flow.shape
+        out = torch.empty(N, D, f * H, f * W, dtype=torch.float32, device=flow.device)
+        _call("stx_convex_upsample_fwd", _p(flow), _p(mask), _p(out), N, D, H, W, mask.shape[1], f, scale)
+        ctx.save_for_backward(flow, mask)
+        ctx.cfg = (f, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        flow, mask = ctx.saved_tensors
+        f, scale = ctx.cfg
+        N, D, H, W = flow.shape
+        gf = torch.empty_like(flow) if ctx.needs_input_grad[0] else None
+        gm = torch.empty_like(mask) if ctx.needs_input_grad[1] else None
+        ws = None
+        if gf is not None:
+            ws = _WS.get("convex_upsample_bwd", get_lib().raw("stx_convex_upsample_bwd_workspace_floats")(N, D, H, W), flow.device)
+        _call("stx_convex_upsample_bwd", _p(_aligned16(g.contiguous())), _p(flow), _p(mask), _p(gf), _p(gm), _p(ws), N, D, H, W,
+              mask.shape[1], f, scale)
+        return gf, gm, None, None
+
+
+@fp32_region
+def convex_upsample(flow, mask, n_downsample=2, use_scale_factor=True):
+    """flow [N, D, H, W], mask [N, 9 * 4^n, H, W] (the LOGITS of the mask head) -> [N, D, 2^n H, 2^n W]: the soft-max over the nine
+    taps and the convex combination of the 3 x 3 neighbourhood of 2^n * flow (flow itself with use_scale_factor=False), one launch.
+    n_downsample 1, 2 or 3.  A fp16 / bf16 mask (the reference's autocast) is taken as its fp32 cast and gets its gradient back in
+    its own dtype; the flow is fp32.  Differentiable in both."""
+    who = "convex_upsample"
+    if flow.dim() != 4 or mask.dim() != 4:
+        raise StxError(f"{who}: flow must be [N, D, H, W] and mask [N, 9 * 4^n, H, W], got {tuple(flow.shape)} / {tuple(mask.shape)}")
+    if not isinstance(n_downsample, int) or 2 ** n_downsample not in CONVEX_FACTORS:
+        raise StxError(f"{who}: n_downsample {n_downsample!r} is not built (factors {CONVEX_FACTORS}); flow {tuple(flow.shape)}, "
+                       f"mask {tuple(mask.shape)}")
+    f = 2 ** n_downsample
+    N, D, H, W = flow.shape
+    if D < 1 or mask.shape != (N, 9 * f * f, H, W):
+        raise StxError(f"{who}: flow {tuple(flow.shape)} at n_downsample={n_downsample} wants mask {(N, 9 * f * f, H, W)}, got "
+                       f"{tuple(mask.shape)}")
+    if mask.dtype in _LOW:
+        mask = mask.float()
+    flow, mask = flow.contiguous(), mask.contiguous()
+    _chk(flow, "flow", 4)
+    _chk(mask, "mask", 4)
+    scale = float(f) if use_scale_factor else 1.0
+    if torch.is_grad_enabled() and (flow.requires_grad or mask.requires_grad):
+        return ConvexUpsampleFn.apply(flow, mask, f, scale)
+    return ConvexUpsampleFn.forward(_NoCtx(), flow, mask, f, scale)
+
+
+class SoftmaxContextUpsampleFn(torch.autograd.Function):
+    """context_upsample(scale * disp_low, softmax(logits, 1)) (IGEVStereo/igev_stereo.py:158-166) on
+    stx_softmax_context_upsample_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, disp_low, logits, scale):
+        B, _, h, w = disp_low.shape
+        out = torch.empty(B, 4 * h, 4 * w, dtype=torch.float32, device=disp_low.device)
+        _call("stx_softmax_context_upsample_fwd", _p(disp_low), _p(logits), _p(out), B, h, w, scale)
+        ctx.save_for_backward(disp_low, logits)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        disp_low, logits = ctx.saved_tensors
+        B, _, h, w = disp_low.shape
+        gd = torch.empty_like(disp_low) if ctx.needs_input_grad[0] else None
+        gl = torch.empty_like(logits) if ctx.needs_input_grad[1] else None
+        ws = None
+        if gd is not None:
+            ws = _WS.get("convex_upsample_bwd", get_lib().raw("stx_convex_upsample_bwd_workspace_floats")(B, 1, h, w), disp_low.device)
+        _call("stx_softmax_context_upsample_bwd", _p(_aligned16(g.contiguous())), _p(disp_low), _p(logits), _p(gd), _p(gl), _p(ws), B, h, w,
+              ctx.scale)
+        return gd, gl, None
+
+
+@fp32_region
+def softmax_context_upsample(disp_low, logits, scale=4.0):
+    """disp_low [B, 1, h, w], logits [B, 9, 4h, 4w] -> [B, 4h, 4w] = context_upsample(scale * disp_low, softmax(logits, 1)) without
+    the full-resolution soft-max pass or its saved output.  Differentiable in both."""
+    who = "softmax_context_upsample"
+    if disp_low.dim() != 4 or logits.dim() != 4 or disp_low.shape[1] != 1 or \
+            logits.shape != (disp_low.shape[0], 9, 4 * disp_low.shape[2], 4 * disp_low.shape[3]):
+        raise StxError(f"{who}: disp_low [B, 1, h, w] wants logits [B, 9, 4h, 4w], got {tuple(disp_low.shape)} / {tuple(logits.shape)}")
+    if logits.dtype in _LOW:
+        logits = logits.float()
+    disp_low, logits = disp_low.contiguous(), _aligned16(logits.contiguous())
+    _chk(disp_low, "disp_low", 4)
+    _chk(logits, "logits", 4)
+    if torch.is_grad_enabled() and (disp_low.requires_grad or logits.requires_grad):
+        return SoftmaxContextUpsampleFn.apply(disp_low, logits, float(scale))
+    return SoftmaxContextUpsampleFn.forward(_NoCtx(), disp_low, logits, float(scale))
+
+
+def sequence_loss_max_predictions():
+    return int(get_lib().raw("stx_sequence_loss_max_predictions")())
+
+
+def _pointer_table(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+class SequenceLossFn(torch.autograd.Function):
+    """The trainer's loss over a list of predictions (trainer/trainer_torchrun.py:272-284) on stx_sequence_loss_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, gt, maxdisp, weights, *preds):
+        K, n = len(preds), gt.numel()
+        out = torch.empty(2, dtype=torch.float32, device=gt.device)            # the loss and, as an int, the valid count
+        count = out[1:].view(torch.int32)
+        ws = _WS.get("sequence_loss", get_lib().raw("stx_sequence_loss_workspace_floats")(n), gt.device)
+        wts = (ctypes.c_double * K)(*weights)
+        _call("stx_sequence_loss_fwd", _pointer_table(preds), wts, K, _p(gt), maxdisp, _p(out), _p(count), _p(ws), n)
+        ctx.save_for_backward(gt, count, *preds)
+        ctx.cfg = (maxdisp, tuple(weights))
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        gt, count, *preds = ctx.saved_tensors
+        maxdisp, weights = ctx.cfg
+        K, n = len(preds), gt.numel()
+        needs = ctx.needs_input_grad[3:]
+        slab = torch.empty(sum(needs), n, dtype=torch.float32, device=gt.device)
+        rows = iter(slab)
+        grads = [next(rows).view(p.shape) if need else None for p, need in zip(preds, needs)]
+        wts = (ctypes.c_double * K)(*weights)
+        _call("stx_sequence_loss_bwd", _p(g.contiguous()), _pointer_table(preds), wts, K, _p(gt), maxdisp, _p(count),
+              _pointer_table(grads), n)
+        return (None, None, None, *grads)
+
+
+def sequence_loss(preds, gt, maxdisp, weights):
+    """sum_k weights[k] * mean_valid smooth_l1(preds[k], gt), valid = (gt > 0) & (gt < maxdisp - 1): the value of
+    losses.masked_smooth_l1_multi, every prediction in ONE launch forward and one backward, no host sync.  preds: a list of
+    [B, H, W] or [B, 1, H, W] fp32 tensors of gt's size; an empty mask gives 0 (and zero gradients); NaN / inf in gt is excluded."""
+    who = "sequence_loss"
+    preds, weights = list(preds), [float(w) for w in weights]
+    if len(preds) != len(weights):
+        raise ValueError(f"{who}: {len(preds)} predictions but {len(weights)} weights")
+    limit = sequence_loss_max_predictions()
+    if not 1 <= len(preds) <= limit:
+        raise StxError(f"{who}: {len(preds)} predictions, one launch takes 1..{limit}")
+    gt = gt.contiguous()
+    _chk(gt, "gt")
+    shape = tuple(gt.shape[:1]) + tuple(gt.shape[-2:])
+    if gt.dim() not in (3, 4) or gt.numel() != shape[0] * shape[1] * shape[2]:
+        raise StxError(f"{who}: gt must be [B, H, W] or [B, 1, H, W], got {tuple(gt.shape)}")
+    dense = []
+    for k, p in enumerate(preds):
+        if p.dim() not in (3, 4) or tuple(p.shape[:1]) + tuple(p.shape[-2:]) != shape or p.numel() != gt.numel():
+            raise StxError(f"{who}: prediction {k} is {tuple(p.shape)}, gt {tuple(gt.shape)}")
+        p = p.contiguous()
+        _chk(p, f"preds[{k}]")
+        dense.append(p)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in dense):
+        return SequenceLossFn.apply(gt, float(maxdisp), weights, *dense)
+    return SequenceLossFn.forward(_NoCtx(), gt, float(maxdisp), weights, *dense)
+
+
 # --------------------------------------------------------------------------------------- self-supervised losses
 SSIM_WINDOWS = (3, 5, 7, 9, 11)                                          # csrc/selfsup_loss.hip SL_MAX_PAD
 PHOTO_WINDOW = 7                                                         # photometric_loss calls ssim() with its default
