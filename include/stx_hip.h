@@ -421,6 +421,49 @@ int stx_corr1d_volume_pyramid_bwd(const float* gcpyr, const float* tdisp, const 
 int stx_truncate_mask_fwd(const float* disp, const float* conf, int has_th, float conf_th, float atten, float* mask, int B, int H,
                           int W, void* stream);
 
+/* ---- mono_align.hip: StereoAnywhere's mono-stereo alignment stage (stereoanywhere.py:167-235) ------------------------------
+ * The bin rule of generate_masks (utils/utils.py:48-54): channel i where f32(i / N) <= mde < f32((i + 1) / N), compared in fp32;
+ *   values >= 1, negative values and NaN fall in no bin.  1 <= N <= 64.
+ * stx_generate_masks_fwd: mde [B][1][H][W] -> masks [B][N][H][W] as fp16 (2-byte elements, 1.0 or 0.0), every element written.
+ * stx_masked_volume_fwd: vol [B][1][H][W2][W3], mde_l [B][1][H][W2], mde_r [B][1][H][W3] -> out [B][N][H][W2][W3] =
+ *   volume * left_masks.unsqueeze(4) * right_masks.unsqueeze(3): out[n] = vol where both bins are n, exact zero elsewhere (also
+ *   where vol is not finite).  Every element written once.  W3 <= 2048, B*N*H*W2*W3 < 2^40.
+ * stx_masked_volume_bwd: g [B][N][H][W2][W3] -> gvol [B][1][H][W2][W3] = g[bin_left] where the two bins agree, else 0; one
+ *   gather, no atomics.  The maps carry no gradient.
+ * stx_softlrc_fwd (utils/utils.py:172-198): disp2, disp3 [B][1][H][W] -> out2 = softplus(lrc_th - |disp2 - warp(disp3)|) /
+ *   log(1 + e^lrc_th) and out3 likewise, the warp bilinear in both directions with zeros outside at column
+ *   (x -+ relu(d)) (W - 1) / W and row y (H - 1) / H; one launch.  lrc_th <= 20, B*H*W < 2^31.
+ * stx_softlrc_bwd: g2 / g3 (either may be NULL) -> gdisp2, gdisp3 through the direct term, the sampled value and the sample
+ *   coordinate (with the gate of relu); two launches, no atomics, bitwise reproducible.  workspace =
+ *   stx_softlrc_bwd_workspace_floats floats, 8-byte aligned.  W <= 1024.
+ * stx_weighted_lsq_fwd (utils/utils.py:345-384): per image b over its n elements, s = relu(disp): the two thresholds are
+ *   torch.quantile's fp32 results (order statistics by radix select, its `lerp`), the mask t_min <= s <= t_max, weights
+ *   0.9 |conf| + 0.1, m = |mde|; the five sums S_wmm, S_wm, S_w, S_wms, S_ws in double in a fixed order; scale [B], shift [B]
+ *   from the 2 x 2 normal equations (determinant 0: scale 0, shift S_ws / S_w).  stats: 8 doubles per image (the five sums, the
+ *   two thresholds, 0), 8-byte aligned.  One launch, one workgroup per image; n < 2^24, B <= 65535, 0 <= quantiles <= 1.
+ * stx_weighted_lsq_bwd: g_scale / g_shift [B] (either may be NULL) and the forward's stats -> g_mde, g_disp, g_conf [B][n],
+ *   every element written; the thresholds carry no gradient.
+ * stx_mirror_detector_fwd / _bwd (utils/utils.py:255-269): elementwise over n pixels; the backward writes all four gradients. */
+int stx_generate_masks_fwd(const float* mde, void* masks, int B, int N, int H, int W, void* stream);
+int stx_masked_volume_fwd(const float* vol, const float* mde_l, const float* mde_r, float* out, int B, int N, int H, int W2, int W3,
+                          void* stream);
+int stx_masked_volume_bwd(const float* g, const float* mde_l, const float* mde_r, float* gvol, int B, int N, int H, int W2, int W3,
+                          void* stream);
+int stx_softlrc_fwd(const float* disp2, const float* disp3, float lrc_th, float* out2, float* out3, int B, int H, int W,
+                    void* stream);
+long long stx_softlrc_bwd_workspace_floats(int B, int H, int W);
+int stx_softlrc_bwd(const float* g2, const float* g3, const float* disp2, const float* disp3, float lrc_th, void* workspace,
+                    float* gdisp2, float* gdisp3, int B, int H, int W, void* stream);
+int stx_weighted_lsq_fwd(const float* mde, const float* disp, const float* conf, float min_quantile, float max_quantile, float* scale,
+                         float* shift, void* stats, int B, long long n, void* stream);
+int stx_weighted_lsq_bwd(const float* g_scale, const float* g_shift, const float* mde, const float* disp, const float* conf,
+                         const void* stats, float* g_mde, float* g_disp, float* g_conf, int B, long long n, void* stream);
+int stx_mirror_detector_fwd(const float* stereo_disp, const float* mono_disp, const float* stereo_conf, const float* mono_conf,
+                            float conf_th, float step_gain, float* out, long long n, void* stream);
+int stx_mirror_detector_bwd(const float* g_out, const float* stereo_disp, const float* mono_disp, const float* stereo_conf,
+                            const float* mono_conf, float conf_th, float step_gain, float* g_stereo_disp, float* g_mono_disp,
+                            float* g_stereo_conf, float* g_mono_conf, long long n, void* stream);
+
 /* ---- selfsup_loss.hip: the self-supervised objective (reference loss_functions/), NCHW fp32 ----------------------------------
  * All reductions are deterministic (no float atomics, sums in double); every output element is written once.
  * stx_photo_warp_fwd (photometric_loss.py:5-37): warped [B][C][H][W] = right sampled bilinearly in both directions, zeros

@@ -114,6 +114,17 @@ SIGNATURES = {
     "stx_corr1d_volume_pyramid_fwd": [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
     "stx_corr1d_volume_pyramid_bwd": [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
     "stx_truncate_mask_fwd": [_P, _P, _I, _F, _F, _P, _I, _I, _I, _P],
+    # mono_align.hip
+    "stx_generate_masks_fwd": [_P, _P, _I, _I, _I, _I, _P],
+    "stx_masked_volume_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "stx_masked_volume_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "stx_softlrc_fwd": [_P, _P, _F, _P, _P, _I, _I, _I, _P],
+    "stx_softlrc_bwd_workspace_floats": [_I, _I, _I],
+    "stx_softlrc_bwd": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
+    "stx_weighted_lsq_fwd": [_P, _P, _P, _F, _F, _P, _P, _P, _I, _L, _P],
+    "stx_weighted_lsq_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _P],
+    "stx_mirror_detector_fwd": [_P, _P, _P, _P, _F, _F, _P, _L, _P],
+    "stx_mirror_detector_bwd": [_P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _L, _P],
     # selfsup_loss.hip
     "stx_photo_warp_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "stx_photo_warp_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],

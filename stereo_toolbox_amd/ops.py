@@ -2032,6 +2032,237 @@ def truncate_mask(disp_left, conf_left, conf_th=0.5, attenuation_gain=0.1):
     return mask
 
 
+# --------------------------------------------------------------------------------------- StereoAnywhere mono-stereo alignment
+MASKS_MAX_N = 64                                                         # csrc/mono_align.hip MA_MAX_N
+MASKED_VOLUME_MAX_W = 2048                                               # MA_MAX_W
+SOFTLRC_MAX_TH = 20.0                                                    # the linear branch of F.softplus starts above
+SOFTLRC_BWD_MAX_W = 1024                                                 # MA_LRC_MAX_W
+WEIGHTED_LSQ_MAX_N = 1 << 24                                             # torch.quantile's own limit
+
+
+def _maps(who, shape_of, **maps):
+    """Dense fp32 device maps of one shape [B, C, H, W] (`shape_of` names the first); refuses before any launch."""
+    out, want = [], None
+    for name, t in maps.items():
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or (shape_of == 1 and t.shape[1] != 1):
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise StxError(f"{who}: {name} must be [B, {'1' if shape_of == 1 else 'C'}, H, W], got {got}")
+        if want is None:
+            want = t.shape
+        elif t.shape != want:
+            raise StxError(f"{who}: {name} {tuple(t.shape)} does not match {tuple(want)}")
+        t = t.contiguous()
+        _chk(t, name, 4)
+        out.append(t)
+    return out
+
+
+def _n_masks(who, N):
+    if not isinstance(N, int) or isinstance(N, bool) or not 1 <= N <= MASKS_MAX_N:
+        raise StxError(f"{who}: the number of masks must be an int in 1..{MASKS_MAX_N}, got {N!r}")
+    return N
+
+
+def generate_masks(mde, N=16):
+    """generate_masks (StereoAnywhere/utils/utils.py:48-54): mde [B, 1, H, W] -> one-hot fp16 masks [B, N, H, W], channel i where
+    f32(i / N) <= mde < f32((i + 1) / N) compared in fp32; values >= 1, negative values and NaN fall in no bin.  No gradient."""
+    N = _n_masks("generate_masks", N)
+    mde, = _maps("generate_masks", 1, mde=mde.detach() if isinstance(mde, torch.Tensor) else mde)
+    B, _, H, W = mde.shape
+    masks = torch.empty(B, N, H, W, dtype=torch.float16, device=mde.device)
+    _call("stx_generate_masks_fwd", _p(mde), _p(masks), B, N, H, W)
+    return masks
+
+
+class MaskedVolumeFn(torch.autograd.Function):
+    """volume * left_masks.unsqueeze(4) * right_masks.unsqueeze(3) (stereoanywhere.py:180,193) on stx_masked_volume_fwd / _bwd: the
+    volume row is read once, the N output rows are written once; the backward gathers one channel row."""
+
+    @staticmethod
+    def forward(ctx, vol, ml, mr, N):
+        B, H, W2, W3 = vol.shape
+        out = torch.empty(B, N, H, W2, W3, dtype=torch.float32, device=vol.device)
+        _call("stx_masked_volume_fwd", _p(vol), _p(ml), _p(mr), _p(out), B, N, H, W2, W3)
+        ctx.save_for_backward(ml, mr)
+        ctx.cfg = (B, N, H, W2, W3)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ml, mr = ctx.saved_tensors
+        B, N, H, W2, W3 = ctx.cfg
+        gvol = torch.empty(B, H, W2, W3, dtype=torch.float32, device=g.device)
+        _call("stx_masked_volume_bwd", _p(g.contiguous()), _p(ml), _p(mr), _p(gvol), B, N, H, W2, W3)
+        return gvol, None, None, None
+
+
+@fp32_region
+def masked_volume(volume, mde_left, mde_right, n_masks):
+    """volume [B, 1, H, W2, W3], mde_left [B, 1, H, W2], mde_right [B, 1, H, W3] -> contiguous fp32 [B, N, H, W2, W3] equal to
+    volume * generate_masks(mde_left, N).unsqueeze(4) * generate_masks(mde_right, N).unsqueeze(3): out[n] = volume where both
+    bins are n, exact zero elsewhere -- also where the volume is not finite (the reference's product gives NaN there).
+    Differentiated with respect to the volume; the maps carry no gradient (the reference's masks are fp16 constants).  The maps
+    are at the volume's resolution: for the reference's vol_downsample > 0 path (nearest-interpolated masks) pass the strided maps."""
+    N = _n_masks("masked_volume", n_masks)
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 5 or volume.shape[1] != 1:
+        raise StxError(f"masked_volume: the volume must be [B, 1, H, W2, W3], got {tuple(getattr(volume, 'shape', ()))}")
+    for name, t in (("mde_left", mde_left), ("mde_right", mde_right)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != 1:
+            raise StxError(f"masked_volume: {name} must be [B, 1, H, W], got {tuple(getattr(t, 'shape', ()))}")
+    B, _, H, W2, W3 = volume.shape
+    if tuple(mde_left.shape) != (B, 1, H, W2) or tuple(mde_right.shape) != (B, 1, H, W3):
+        raise StxError(f"masked_volume: maps {tuple(mde_left.shape)} / {tuple(mde_right.shape)} do not match the volume "
+                       f"{tuple(volume.shape)}")
+    if W3 > MASKED_VOLUME_MAX_W:
+        raise StxError(f"masked_volume: W3={W3} above the supported {MASKED_VOLUME_MAX_W}")
+    vol, ml, mr = volume[:, 0].contiguous(), mde_left.detach().contiguous(), mde_right.detach().contiguous()
+    _chk(vol, "volume", 4)
+    _chk(ml, "mde_left", 4)
+    _chk(mr, "mde_right", 4)
+    if torch.is_grad_enabled() and vol.requires_grad:
+        return MaskedVolumeFn.apply(vol, ml, mr, N)
+    return MaskedVolumeFn.forward(_NoCtx(), vol, ml, mr, N)
+
+
+class SoftLrcFn(torch.autograd.Function):
+    """softlrc (StereoAnywhere/utils/utils.py:189-198) on stx_softlrc_fwd / _bwd: both maps from one launch; the backward
+    (direct term, sampled value, sample coordinate through relu) in two launches without atomics."""
+
+    @staticmethod
+    def forward(ctx, d2, d3, th):
+        B, _, H, W = d2.shape
+        out2, out3 = torch.empty_like(d2), torch.empty_like(d2)
+        _call("stx_softlrc_fwd", _p(d2), _p(d3), th, _p(out2), _p(out3), B, H, W)
+        if not isinstance(ctx, _NoCtx):
+            ctx.set_materialize_grads(False)
+        ctx.save_for_backward(d2, d3)
+        ctx.th = th
+        return out2, out3
+
+    @staticmethod
+    def backward(ctx, g2, g3):
+        d2, d3 = ctx.saved_tensors
+        B, _, H, W = d2.shape
+        if g2 is None and g3 is None:
+            return None, None, None
+        g2, g3 = (None if g is None else g.contiguous() for g in (g2, g3))
+        ws = torch.empty(4 * B * H * W, dtype=torch.float64, device=d2.device)
+        gd2, gd3 = torch.empty_like(d2), torch.empty_like(d3)
+        _call("stx_softlrc_bwd", _p(g2), _p(g3), _p(d2), _p(d3), ctx.th, _p(ws), _p(gd2), _p(gd3), B, H, W)
+        return gd2, gd3, None
+
+
+@fp32_region
+def softlrc(disp2, disp3, lrc_th=1.0):
+    """disp2, disp3 [B, 1, H, W] -> (softlrc2, softlrc3) = softplus(lrc_th - |disp - warped other|) / log(1 + e^lrc_th), the warp
+    the reference's disp_warping (bilinear in both directions, zeros outside, relu on the warping disparity).  lrc_th <= 20."""
+    if isinstance(lrc_th, bool) or not isinstance(lrc_th, (int, float)) or not lrc_th <= SOFTLRC_MAX_TH:
+        raise StxError(f"softlrc: lrc_th must be a number <= {SOFTLRC_MAX_TH} (above it F.softplus turns linear), got {lrc_th!r}")
+    d2, d3 = _maps("softlrc", 1, disp2=disp2, disp3=disp3)
+    if torch.is_grad_enabled() and (d2.requires_grad or d3.requires_grad):
+        if d2.shape[3] > SOFTLRC_BWD_MAX_W:
+            raise StxError(f"softlrc: W={d2.shape[3]} above the {SOFTLRC_BWD_MAX_W} the backward supports")
+        return SoftLrcFn.apply(d2, d3, float(lrc_th))
+    return SoftLrcFn.forward(_NoCtx(), d2, d3, float(lrc_th))
+
+
+class WeightedLsqFn(torch.autograd.Function):
+    """weighted_lsq (StereoAnywhere/utils/utils.py:345-384) on stx_weighted_lsq_fwd / _bwd: one workgroup per image selects the
+    quantile thresholds, sums and solves; nothing is read back by the host."""
+
+    @staticmethod
+    def forward(ctx, mde, disp, conf, qmin, qmax):
+        B = mde.shape[0]
+        n = mde.numel() // B
+        scale = torch.empty(B, dtype=torch.float32, device=mde.device)
+        shift = torch.empty(B, dtype=torch.float32, device=mde.device)
+        stats = torch.empty(B, 8, dtype=torch.float64, device=mde.device)
+        _call("stx_weighted_lsq_fwd", _p(mde), _p(disp), _p(conf), qmin, qmax, _p(scale), _p(shift), _p(stats), B, n)
+        if not isinstance(ctx, _NoCtx):
+            ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(stats)
+        ctx.save_for_backward(mde, disp, conf, stats)
+        return scale, shift, stats
+
+    @staticmethod
+    def backward(ctx, g_scale, g_shift, _g_stats):
+        mde, disp, conf, stats = ctx.saved_tensors
+        if g_scale is None and g_shift is None:
+            return None, None, None, None, None
+        B = mde.shape[0]
+        g_scale, g_shift = (None if g is None else g.contiguous() for g in (g_scale, g_shift))
+        grads = [torch.empty_like(t) for t in (mde, disp, conf)]
+        _call("stx_weighted_lsq_bwd", _p(g_scale), _p(g_shift), _p(mde), _p(disp), _p(conf), _p(stats), *(_p(g) for g in grads), B,
+              mde.numel() // B)
+        return (*grads, None, None)
+
+
+def _weighted_lsq(mde, disp, conf, min_quantile, max_quantile):
+    for name, q in (("min_quantile", min_quantile), ("max_quantile", max_quantile)):
+        if isinstance(q, bool) or not isinstance(q, (int, float)) or not 0.0 <= q <= 1.0:
+            raise StxError(f"weighted_lsq: {name} must be a number in 0..1, got {q!r}")
+    mde, disp, conf = _maps("weighted_lsq", 0, mde=mde, disp=disp, conf=conf)
+    n = mde.numel() // max(1, mde.shape[0])
+    if not 0 < n < WEIGHTED_LSQ_MAX_N:
+        raise StxError(f"weighted_lsq: {n} elements per image outside 1..2^24 - 1 (the limit of torch.quantile itself)")
+    if torch.is_grad_enabled() and (mde.requires_grad or disp.requires_grad or conf.requires_grad):
+        return WeightedLsqFn.apply(mde, disp, conf, float(min_quantile), float(max_quantile))
+    return WeightedLsqFn.forward(_NoCtx(), mde, disp, conf, float(min_quantile), float(max_quantile))
+
+
+@fp32_region
+def weighted_lsq(mde, disp, conf, min_quantile=0.2, max_quantile=0.9):
+    """mde, disp, conf [B, C, H, W] -> (scale, shift), each [B, 1, 1, 1]: per image the weighted least-squares fit
+    relu(disp) ~ scale |mde| + shift with weights 0.9 |conf| + 0.1 over the elements whose relu(disp) lies between its
+    min_quantile and max_quantile (torch.quantile's fp32 values, bit for bit), from the 2 x 2 normal equations -- the solution the
+    reference gets by QR.  Where their determinant is 0 (one distinct |mde|): scale 0, shift the weighted mean of relu(disp)
+    (the reference's lstsq result there depends on the driver).  Inputs must be finite.  No host synchronisation."""
+    scale, shift, _ = _weighted_lsq(mde, disp, conf, min_quantile, max_quantile)
+    B = scale.shape[0]
+    return scale.view(B, 1, 1, 1), shift.view(B, 1, 1, 1)
+
+
+@fp32_region
+def quantile_thresholds(disp, min_quantile=0.2, max_quantile=0.9):
+    """The two thresholds `weighted_lsq` masks with, [B, 2] fp32: torch.quantile(relu(disp[b]).flatten(), q) for both q."""
+    with torch.no_grad():
+        _, _, stats = _weighted_lsq(disp, disp, disp, min_quantile, max_quantile)
+    return stats[:, 5:7].float()
+
+
+class MirrorDetectorFn(torch.autograd.Function):
+    """handcrafted_mirror_detector (StereoAnywhere/utils/utils.py:255-269) on stx_mirror_detector_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, sd, md, sc, mc, th, gain):
+        out = torch.empty_like(sd)
+        _call("stx_mirror_detector_fwd", _p(sd), _p(md), _p(sc), _p(mc), th, gain, _p(out), sd.numel())
+        ctx.save_for_backward(sd, md, sc, mc)
+        ctx.cfg = (th, gain)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        sd, md, sc, mc = ctx.saved_tensors
+        grads = [torch.empty_like(sd) for _ in range(4)]
+        _call("stx_mirror_detector_bwd", _p(g.contiguous()), _p(sd), _p(md), _p(sc), _p(mc), *ctx.cfg, *(_p(t) for t in grads),
+              sd.numel())
+        return (*grads, None, None)
+
+
+@fp32_region
+def mirror_detector(stereo_disp, mono_disp, stereo_conf, mono_conf, conf_th=0.5, step_gain=20):
+    """Four maps of one shape [B, C, H, W] -> sigmoid(step_gain (fuzzy_or(a, b) - conf_th)) with a = stereo_conf mono_conf
+    sigmoid(step_gain (mono_disp - stereo_disp)), b = (1 - stereo_conf) mono_conf; differentiated with respect to all four."""
+    for name, v in (("conf_th", conf_th), ("step_gain", step_gain)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise StxError(f"mirror_detector: {name} must be a number, got {v!r}")
+    maps = _maps("mirror_detector", 0, stereo_disp=stereo_disp, mono_disp=mono_disp, stereo_conf=stereo_conf, mono_conf=mono_conf)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in maps):
+        return MirrorDetectorFn.apply(*maps, float(conf_th), float(step_gain))
+    return MirrorDetectorFn.forward(_NoCtx(), *maps, float(conf_th), float(step_gain))
+
+
 class ContextUpsampleFn(torch.autograd.Function):
     """context_upsample (IGEVStereo/submodule.py:243-255) on stx_context_upsample_fwd / _bwd."""
 
