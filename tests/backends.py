@@ -62,6 +62,17 @@ def ncdhw(t):
     return t.permute(0, 4, 1, 2, 3).contiguous()
 
 
+def pack(be, w, mode):
+    """w [A][B][T] in the MFMA operand order of stx_conv3d_pack_weight (the modes: include/stx_hip.h)."""
+    A, Bd = w.shape[0], w.shape[1]
+    T = w[0, 0].numel()
+    K, N = (Bd, A) if mode == 0 else (A, Bd)
+    n = be.raw("stx_conv3d_packed_floats")(K, N, T)
+    wp = be.empty(n)
+    be.call("stx_conv3d_pack_weight", ptr(be.dev(w)), ptr(wp), A, Bd, T, mode)
+    return wp
+
+
 BACKENDS = ["emu", pytest.param("hip", marks=pytest.mark.gpu)]
 
 

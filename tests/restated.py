@@ -1,0 +1,71 @@
+"""Plain-torch restatements of reference code that more than one test module compares with: the gather form (no grid_sample)
+of IGEV's geometry lookup (reference models/IGEVStereo/geometry.py:7-70) and convex upsampling (submodule.py:243-255), and
+StereoAnywhere's truncation mask (utils/utils.py:216-238).  A restatement used by a single test module lives in that module.
+"""
+import torch
+
+
+def pool(x):
+    """avg_pool2d(x, [1, 2], stride=[1, 2]) along the last axis: pairs (2j, 2j+1), an odd tail dropped."""
+    n = x.shape[-1] // 2
+    return (x[..., 0:2 * n:2] + x[..., 1:2 * n:2]) / 2
+
+
+def pyramids(geo, f1, f2, levels):
+    """geo [B,C,D,H,W], f1 [B,Cf,H,W], f2 [B,Cf,H,W2] -> ([B,H,W,C,D_i]), ([B,H,W,W2_i])"""
+    gp = [geo.permute(0, 3, 4, 1, 2)]
+    cp = [torch.einsum("aijk,aijh->ajkh", f1, f2)]
+    for _ in range(levels - 1):
+        gp.append(pool(gp[-1]))
+        cp.append(pool(cp[-1]))
+    return gp, cp
+
+
+def sample(rows, x):
+    """rows [..., n], x [..., K] positions -> linear interpolation between floor(x) and floor(x) + 1, zero outside [0, n-1]."""
+    n = rows.shape[-1]
+    x0 = torch.floor(x)
+    f = x - x0
+    i0 = x0.long()
+
+    def tap(i):
+        ok = (i >= 0) & (i < n)
+        return torch.gather(rows, -1, i.clamp(0, n - 1)) * ok.to(rows.dtype)
+    return (1 - f) * tap(i0) + f * tap(i0 + 1)
+
+
+def lookup(gp, cp, disp, coords, radius):
+    B, _, H, W = disp.shape
+    dx = torch.arange(-radius, radius + 1, dtype=disp.dtype, device=disp.device)
+    d, c = disp.reshape(B, H, W, 1), coords.reshape(B, H, W, 1)
+    out = []
+    for i, (g, r) in enumerate(zip(gp, cp)):
+        C = g.shape[3]
+        xg = (d / 2 ** i + dx).unsqueeze(3).expand(B, H, W, C, 2 * radius + 1)
+        out.append(sample(g, xg).reshape(B, H, W, -1))
+        out.append(sample(r, c / 2 ** i - d / 2 ** i + dx))
+    return torch.cat(out, dim=-1).permute(0, 3, 1, 2).contiguous()
+
+
+def upsample(disp_low, wts):
+    B, _, h, w = disp_low.shape
+    p = torch.nn.functional.pad(disp_low[:, 0], (1, 1, 1, 1))
+    out = 0
+    for t in range(9):
+        tap = p[:, t // 3:t // 3 + h, t % 3:t % 3 + w]
+        out = out + wts[:, t] * tap.repeat_interleave(4, 1).repeat_interleave(4, 2)
+    return out
+
+
+def _pack(levels_list):
+    """pixel-major levels ([rows..., len_i(, C)]) -> the flat pyramid buffer of include/stx_hip.h"""
+    return torch.cat([t.reshape(-1) for t in levels_list])
+
+
+def truncation_mask(disp, conf, conf_th, atten):
+    """[B,1,H,W] x 2 -> [B,1,H,W,W], utils/utils.py:216-238"""
+    W = disp.shape[3]
+    a = torch.arange(W, dtype=disp.dtype)
+    c = (conf if conf_th is None else (conf > conf_th).to(disp.dtype)).unsqueeze(4)
+    x = (a.view(1, 1, 1, W) - disp).unsqueeze(4) - a.view(1, 1, 1, 1, W)
+    return 1 * (1 - c) + c * (torch.sigmoid(x) * (1 - atten) + atten)

@@ -17,12 +17,7 @@ import pytest
 import torch
 
 from stereo_toolbox_amd.utils import fill_state_dict, synthetic_tensor
-from tests.test_models import Env, LOSS_W, _filled  # noqa: F401
-
-
-@pytest.fixture(params=["emu", pytest.param("hip", marks=pytest.mark.gpu)])
-def env(request):
-    return Env(request.param)
+from tests.parity import LOSS_W, env, filled  # noqa: F401
 
 
 def _train_iteration(model, data, optimizer, scaler, amp, device, max_disp, low):
@@ -72,7 +67,7 @@ def test_train_iteration_under_autocast(env, ctor, parity_log):
         H, W, D, B = 64, 128, 64, 2
     data = {"left": synthetic_tensor((B, 3, H, W), 1), "right": synthetic_tensor((B, 3, H, W), 2),
             "gt_disp": synthetic_tensor((B, 1, H, W), 3, lo=0.0, hi=float(D - 2))}
-    m, _ = _filled(getattr(models, ctor), D)
+    m, _ = filled(getattr(models, ctor), D)
     m = m.to(dev).train()
     opt = torch.optim.SGD(m.parameters(), lr=0.0)
     scaler = torch.amp.GradScaler(dev.type, init_scale=1024.0)                     # :219 (power of two: scaling is exact in fp32)
@@ -137,7 +132,7 @@ def test_psmnet_aggregate_under_autocast(env):
     dev = env.device
     low = torch.float16 if dev.type == "cuda" else torch.bfloat16
     D, h4, w4 = (32, 8, 16) if env.name == "emu" else (64, 16, 32)
-    m, _ = _filled(models.PSMNet, D)
+    m, _ = filled(models.PSMNet, D)
     m = m.to(dev).train()
     fl = synthetic_tensor((1, 32, h4, w4), 5).to(dev).to(low).requires_grad_()
     fr = synthetic_tensor((1, 32, h4, w4), 6).to(dev).to(low).requires_grad_()

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.backends import be, ptr  # noqa: F401
+from tests.parity import env  # noqa: F401
 
 # B, Cin, Cout, H, W, groups
 CASES = [
@@ -87,26 +88,6 @@ def test_conv2d_refuses_unsupported_shapes(be):
 
 
 # ------------------------------------------------------------------------------------ the product's wiring (features2d)
-class _Env:
-    def __init__(self, name):
-        self.name = name
-        if name == "hip" and not torch.cuda.is_available():
-            pytest.skip("no ROCm device")
-        self.device = torch.device("cuda:0" if name == "hip" else "cpu")
-
-    def ctx(self):
-        import contextlib
-        if self.name == "emu":
-            from tests.emu_util import emu_product_path
-            return emu_product_path()
-        return contextlib.nullcontext()
-
-
-@pytest.fixture(params=["emu", pytest.param("hip", marks=pytest.mark.gpu)])
-def env(request):
-    return _Env(request.param)
-
-
 def test_basic_block_train_step_on_the_own_kernel_matches_the_stock_convolution(env, monkeypatch):
     """A train-mode BasicBlock (models/features2d.py = reference gwcnet.py:24-42) with its two 3x3 convolutions on csrc/conv2d.hip
     (forward, data gradient, fused BatchNorm statistics; the weight gradient stays aten's) against the same block with

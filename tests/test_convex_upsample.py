@@ -9,7 +9,7 @@
   each other.
 * The product (emulator build here, gfx950 with `-m gpu`) is compared with the fp64 fixture, every element of every tensor: values
   within VALUE_FACTOR (2) x d_ref, gradients within GRAD_FACTOR (3) x d_ref; where d_ref is zero the floor 2e-7 * max(1, max|want|)
-  applies.  `_within` prints the achieved ratio.
+  applies (tests/parity.within, which prints the achieved ratio).
 * Where no fixture exists (sequence loss at K = 1, 2, 33; the all-invalid map) the reference is losses.masked_smooth_l1_multi on the
   CPU in fp64, d_ref its own fp32 run's distance from that, the same factors.
 """
@@ -23,8 +23,8 @@ import torch
 from tests.backends import be, ptr  # noqa: F401
 from tests.golden.convex_upsample_config import (CASES, LOSS_GAMMA, LOSS_KS, LOSS_MAXDISP, LOSS_PREDICTIONS, LOSS_SHAPE, PIXEL_CASES,
                                                  PIXEL_SCALE, inputs, loss_inputs, pixel_inputs, trainer_weights)
-from tests.test_geo_lookup import VALUE_FACTOR, _within, env, upsample  # noqa: F401
-from tests.test_models import GRAD_FACTOR
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, env, pin, sync, within, within_fixture  # noqa: F401
+from tests.restated import upsample
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -36,16 +36,6 @@ def gold():
         with np.load(os.path.join(HERE, "golden", name)) as z:
             store.update({k: z[k] for k in z.files})
     return store
-
-
-def _sync(e):
-    if e.name == "hip":
-        torch.cuda.synchronize()
-
-
-def _ref(want64, got32):
-    """A reference formed at test time in the fixture's shape: the fp64 tensor and d_ref of an fp32 evaluation."""
-    return {"x:f64": want64.detach().numpy(), "x:dref": (got32.detach().double() - want64.detach()).abs().max().item()}
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
@@ -73,13 +63,11 @@ def trainer_loss(init_disp, disp_preds, gt, maxdisp, loss_gamma=LOSS_GAMMA):
 
 
 def _pinned(gold, tag, res, dtype):
+    """One dtype per test; a d_ref of zero (an output both reference runs give to the bit) falls back on the floor of `within`."""
     for k, v in res.items():
-        want = torch.from_numpy(gold[f"{tag}:{k}:{'f64' if dtype == torch.float64 else 'f32'}"])
-        peak = max(1.0, float(np.abs(gold[f"{tag}:{k}:f64"]).max()))
-        dref = float(gold[f"{tag}:{k}:dref"])
-        tol = 1e-11 * peak if dtype == torch.float64 else (2 * dref if dref > 0 else 2e-7 * peak)
-        assert v.dtype == want.dtype == dtype and v.shape == want.shape, (tag, k)
-        assert (v.detach() - want).abs().max().item() <= tol, (tag, k, dtype)
+        want64, want32 = torch.from_numpy(gold[f"{tag}:{k}:f64"]), torch.from_numpy(gold[f"{tag}:{k}:f32"])
+        r64, r32 = (v, None) if dtype == torch.float64 else (None, v)
+        pin(r64, r32, want64, want32, float(gold[f"{tag}:{k}:dref"]), f"{tag}:{k}", zero_dref="floor")
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -136,7 +124,7 @@ def _product(env, tag, needs=(True, True), flow_channels=None):  # noqa: F811
     with env.ctx():
         out = ops.convex_upsample(flow, mask, n_downsample=n, use_scale_factor=use_scale)
         (out * gw.to(dev)).sum().backward()
-        _sync(env)
+        sync(env)
     return out.detach(), flow.grad, mask.grad
 
 
@@ -145,9 +133,9 @@ def test_convex_upsample_matches_reference_fp64(env, gold, tag):  # noqa: F811
     N, D, H, W, n, _, _ = CASES[tag]
     out, g_flow, g_mask = _product(env, tag)
     assert out.shape == (N, D, H << n, W << n) and out.dtype == torch.float32 and out.is_contiguous()
-    _within(out, gold, f"{tag}:out", VALUE_FACTOR, f"{tag} out")
-    _within(g_flow, gold, f"{tag}:g_flow", GRAD_FACTOR, f"{tag} g_flow")
-    _within(g_mask, gold, f"{tag}:g_mask", GRAD_FACTOR, f"{tag} g_mask")
+    within_fixture(out, gold, f"{tag}:out", VALUE_FACTOR, f"{tag} out")
+    within_fixture(g_flow, gold, f"{tag}:g_flow", GRAD_FACTOR, f"{tag} g_flow")
+    within_fixture(g_mask, gold, f"{tag}:g_mask", GRAD_FACTOR, f"{tag} g_mask")
     assert g_mask.abs().max().item() > 0
 
 
@@ -173,12 +161,12 @@ def test_softmax_context_upsample_matches_reference_fp64(env, gold, tag):  # noq
         with env.ctx():
             out = fn(d, z)
             (out * gw.to(dev)).sum().backward()
-            _sync(env)
+            sync(env)
         return out.detach(), d.grad, z.grad
     got = run(upsample_disp_from_logits)
     assert got[0].shape == (B, 4 * h, 4 * w) and got[0].dtype == torch.float32 and got[0].is_contiguous()
     for g, k, factor in zip(got, ("out", "g_disp", "g_logits"), (VALUE_FACTOR, GRAD_FACTOR, GRAD_FACTOR)):
-        _within(g, gold, f"{tag}:{k}", factor, f"{tag} {k}")
+        within_fixture(g, gold, f"{tag}:{k}", factor, f"{tag} {k}")
     # the unfused pair the models run today: the existing kernel on stock soft-max weights
     old = run(lambda d, z: ops.context_upsample(PIXEL_SCALE * d, torch.softmax(z, 1)))
     for a, b, k, factor in zip(got, old, ("out", "g_disp", "g_logits"), (VALUE_FACTOR, GRAD_FACTOR, GRAD_FACTOR)):
@@ -228,7 +216,7 @@ def test_fp16_mask_under_autocast_is_its_fp32_cast(env):  # noqa: F811
             out = upsample_flow(f, m, 2)
             assert torch.equal(out, convex_upflow(f, m, n_downsample=2, use_scale_factor=True))
             (out * gw.to(dev)).sum().backward()
-            _sync(env)
+            sync(env)
         res.append((out.detach(), f.grad, m.grad))
     assert res[1][0].dtype == torch.float32 and res[1][2].dtype == torch.float16
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
@@ -250,9 +238,9 @@ def test_kernel_level_convex_upsample(be, gold):  # noqa: F811
     ws = be.empty(nws)
     be.call("stx_convex_upsample_fwd", ptr(flow), ptr(mask), ptr(out), N, D, H, W, 9 * f * f, f, float(f))
     be.call("stx_convex_upsample_bwd", ptr(gw), ptr(flow), ptr(mask), ptr(gf), ptr(gm), ptr(ws), N, D, H, W, 9 * f * f, f, float(f))
-    _within(out, gold, f"{tag}:out", VALUE_FACTOR, "kernel out")
-    _within(gf, gold, f"{tag}:g_flow", GRAD_FACTOR, "kernel g_flow")
-    _within(gm, gold, f"{tag}:g_mask", GRAD_FACTOR, "kernel g_mask")
+    within_fixture(out, gold, f"{tag}:out", VALUE_FACTOR, "kernel out")
+    within_fixture(gf, gold, f"{tag}:g_flow", GRAD_FACTOR, "kernel g_flow")
+    within_fixture(gm, gold, f"{tag}:g_mask", GRAD_FACTOR, "kernel g_mask")
     only_f, only_m = be.empty(N, D, H, W), be.empty(N, 9 * f * f, H, W)
     be.call("stx_convex_upsample_bwd", ptr(gw), ptr(flow), ptr(mask), ptr(only_f), None, ptr(ws), N, D, H, W, 9 * f * f, f, float(f))
     be.call("stx_convex_upsample_bwd", ptr(gw), ptr(flow), ptr(mask), None, ptr(only_m), None, N, D, H, W, 9 * f * f, f, float(f))
@@ -290,9 +278,9 @@ def test_kernel_level_softmax_context_upsample(be, gold):  # noqa: F811
     ws = be.empty(be.raw("stx_convex_upsample_bwd_workspace_floats")(B, 1, h, w))
     be.call("stx_softmax_context_upsample_fwd", ptr(disp), ptr(logits), ptr(out), B, h, w, PIXEL_SCALE)
     be.call("stx_softmax_context_upsample_bwd", ptr(gw), ptr(disp), ptr(logits), ptr(gd), ptr(gl), ptr(ws), B, h, w, PIXEL_SCALE)
-    _within(out, gold, f"{tag}:out", VALUE_FACTOR, "kernel out")
-    _within(gd, gold, f"{tag}:g_disp", GRAD_FACTOR, "kernel g_disp")
-    _within(gl, gold, f"{tag}:g_logits", GRAD_FACTOR, "kernel g_logits")
+    within_fixture(out, gold, f"{tag}:out", VALUE_FACTOR, "kernel out")
+    within_fixture(gd, gold, f"{tag}:g_disp", GRAD_FACTOR, "kernel g_disp")
+    within_fixture(gl, gold, f"{tag}:g_logits", GRAD_FACTOR, "kernel g_logits")
     only_d, only_l = be.empty(B, 1, h, w), be.empty(B, 9, 4 * h, 4 * w)
     be.call("stx_softmax_context_upsample_bwd", ptr(gw), ptr(disp), ptr(logits), ptr(only_d), None, ptr(ws), B, h, w, PIXEL_SCALE)
     be.call("stx_softmax_context_upsample_bwd", ptr(gw), ptr(disp), ptr(logits), None, ptr(only_l), None, B, h, w, PIXEL_SCALE)
@@ -319,7 +307,7 @@ def _loss_product(env, gt, preds, weights, fn=None):  # noqa: F811
     with env.ctx():
         loss = fn(leaves, gt.to(dev)) if fn else ops.sequence_loss(leaves, gt.to(dev), LOSS_MAXDISP, weights)
         loss.backward()
-        _sync(env)
+        sync(env)
     return loss.detach(), torch.stack([p.grad for p in leaves])
 
 
@@ -348,8 +336,9 @@ def test_sequence_loss_equals_masked_smooth_l1_multi(env, K):  # noqa: F811
     (want_l, want_g), (l32, g32) = _multi(gt, preds, w, torch.float64), _multi(gt, preds, w, torch.float32)
     loss, grads = _loss_product(env, gt, preds, w)
     assert loss.shape == () and loss.dtype == torch.float32 and grads.shape == (K, LOSS_SHAPE[0], 1) + LOSS_SHAPE[1:]
-    _within(loss, _ref(want_l, l32), "x", VALUE_FACTOR, f"K={K} loss")
-    _within(grads, _ref(want_g, g32), "x", GRAD_FACTOR, f"K={K} gradients")
+    # (no fixture: d_ref is the distance of the reference's fp32 run from its fp64 run, formed here)
+    within(loss, want_l, (l32.double() - want_l).abs().max().item(), VALUE_FACTOR, f"K={K} loss")
+    within(grads, want_g, (g32.double() - want_g).abs().max().item(), GRAD_FACTOR, f"K={K} gradients")
     excluded = ~((gt > 0) & (gt < LOSS_MAXDISP - 1))
     assert excluded.sum() > 8 and (grads.cpu()[:, excluded.unsqueeze(1)] == 0).all() and torch.isfinite(grads).all()
     again = _loss_product(env, gt, preds, w)
@@ -363,8 +352,8 @@ def test_sequence_loss_matches_the_trainer_fixture(env, gold):  # noqa: F811
     gt, preds = loss_inputs()
     assert sequence_loss_weights(LOSS_PREDICTIONS, LOSS_GAMMA) == trainer_weights(LOSS_PREDICTIONS)
     loss, grads = _loss_product(env, gt, preds, None, fn=lambda p, g: sequence_loss(p[0], p[1:], g, LOSS_MAXDISP, LOSS_GAMMA))
-    _within(loss, gold, "trainer:loss", VALUE_FACTOR, "trainer loss")
-    _within(grads, gold, "trainer:grads", GRAD_FACTOR, "trainer gradients")
+    within_fixture(loss, gold, "trainer:loss", VALUE_FACTOR, "trainer loss")
+    within_fixture(grads, gold, "trainer:grads", GRAD_FACTOR, "trainer gradients")
     with pytest.raises(ValueError):
         sequence_loss_weights(1)
     with pytest.raises(ValueError), env.ctx():
@@ -386,7 +375,7 @@ def test_only_some_predictions_require_grad(env):  # noqa: F811
     leaves = [p.to(dev).clone().requires_grad_(k != 1) for k, p in enumerate(preds)]
     with env.ctx():
         ops.sequence_loss(leaves, gt.to(dev), LOSS_MAXDISP, _weights(3)).backward()
-        _sync(env)
+        sync(env)
     assert leaves[1].grad is None and torch.equal(leaves[0].grad, full[0]) and torch.equal(leaves[2].grad, full[2])
 
 

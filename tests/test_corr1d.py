@@ -28,8 +28,9 @@ import torch
 from tests.backends import be, ptr  # noqa: F401
 from tests.golden.corr1d_config import (ALL_CASES, CASES, DEFOM_SCALE_RADIUS, DEFOM_SCALES, GPU_ONLY_CASES, ITER_CALLS, ITER_CASE,
                                         SHAPE_CASES, SUBSAMPLE, columns, inputs, iter_inputs, out_channels, subsample)
-from tests.test_geo_lookup import EPS, VALUE_FACTOR, _near, _pack, _within, env, pool, sample  # noqa: F401
-from tests.test_models import GRAD_FACTOR, Env
+from tests.parity import (EPS, GRAD_FACTOR, VALUE_FACTOR, Env, env, near, on, pin_fixture, pin_subsample, sync, within,  # noqa: F401
+                          within_fixture)
+from tests.restated import _pack, pool, sample
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "corr1d.npz")
 ITER = f"iter{ITER_CALLS}"
@@ -38,16 +39,6 @@ ITER = f"iter{ITER_CALLS}"
 @pytest.fixture(scope="module")
 def gold():
     return np.load(GOLD)
-
-
-def _on(tags):
-    """(backend, tag): every case on the GPU, on the emulator all but the gpu-only ones."""
-    return [("emu", t) for t in tags if t not in GPU_ONLY_CASES] + [pytest.param("hip", t, marks=pytest.mark.gpu) for t in tags]
-
-
-def _check(got, want64, gold, key, factor):
-    """Every element of `got` against `want64`, within factor x the reference's stored d_ref (`_within` prints the ratio)."""
-    _within(got, {key + ":f64": want64.detach().numpy(), key + ":dref": float(gold[key + ":dref"])}, key, factor, key)
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
@@ -115,26 +106,15 @@ def _restated_iterations():
 def _pinned(r64, gold, tag):
     """The fp64 restatement against the stored subsample of the reference's fp64 tensors."""
     for k, v in r64.items():
-        want = torch.from_numpy(gold[f"{tag}:{k}:sub"])
-        peak = float(gold[f"{tag}:{k}:max"])
-        got = subsample(v.detach())
-        assert got.shape == want.shape and want.numel() >= min(v.numel(), SUBSAMPLE), (tag, k, got.shape, want.shape)
-        assert abs(v.detach().abs().max().item() - peak) <= 1e-11 * max(1.0, peak), (tag, k)
-        assert (got - want).abs().max().item() <= 1e-11 * max(1.0, peak), (tag, k)
+        pin_subsample(v, torch.from_numpy(gold[f"{tag}:{k}:sub"]), float(gold[f"{tag}:{k}:max"]), subsample, min(v.numel(), SUBSAMPLE),
+                      f"{tag}:{k}")
 
 
 @pytest.mark.parametrize("tag", list(CASES))
 def test_restatement_matches_reference_fixture(gold, tag):
     r64, r32 = _restated(tag, torch.float64), _restated(tag, torch.float32)
     for k in r64:
-        want64 = torch.from_numpy(gold[f"{tag}:{k}:f64"])
-        assert r64[k].shape == want64.shape
-        assert (r64[k] - want64).abs().max().item() <= 1e-11 * max(1.0, want64.abs().max().item()), k
-        want32 = torch.from_numpy(gold[f"{tag}:{k}:f32"])
-        assert r32[k].dtype == want32.dtype == torch.float32
-        dref = float(gold[f"{tag}:{k}:dref"])
-        assert dref > 0
-        assert (r32[k] - want32).abs().max().item() <= 2 * dref, k
+        pin_fixture(r64[k], r32[k], gold, f"{tag}:{k}")
 
 
 @pytest.mark.parametrize("tag", list(SHAPE_CASES))
@@ -173,8 +153,7 @@ def _product_case(env, tag, cls=None, needs=(True, True), prepare=None, backward
         loss = sum((o * g.to(dev)).sum() for o, g in zip(outs, gws))
         if backward:
             loss.backward(retain_graph=retain)
-            if env.name == "hip":
-                torch.cuda.synchronize()
+            sync(env)
     return outs, {"g_fmap1": leaves[0].grad, "g_fmap2": leaves[1].grad}, (leaves, loss, fn)
 
 
@@ -193,15 +172,15 @@ def test_lookup_matches_reference_fp64(env, gold, tag):
     for i, k in ((0, "out_a"), (1, "out_b")):
         n = out_channels(tag, scaling=(kind == "defom" and i == 1))
         assert outs[i].shape == (B, n, H, W1) and outs[i].dtype == torch.float32 and outs[i].is_contiguous()
-        _within(outs[i], gold, f"{tag}:{k}", VALUE_FACTOR, f"{tag} {k}")
+        within_fixture(outs[i], gold, f"{tag}:{k}", VALUE_FACTOR, f"{tag} {k}")
     for k, g in grads.items():
-        _within(g, gold, f"{tag}:{k}", GRAD_FACTOR, f"{tag} {k}")
+        within_fixture(g, gold, f"{tag}:{k}", GRAD_FACTOR, f"{tag} {k}")
     corr = _static_corr(env, tag)
     assert corr.shape == (B, H, W1, 1, W2) and corr.dtype == torch.float32 and corr.is_contiguous()
-    _within(corr, gold, f"{tag}:corr", VALUE_FACTOR, f"{tag} corr")
+    within_fixture(corr, gold, f"{tag}:corr", VALUE_FACTOR, f"{tag} corr")
 
 
-@pytest.mark.parametrize("backend,tag", _on(SHAPE_CASES))
+@pytest.mark.parametrize("backend,tag", on(SHAPE_CASES, GPU_ONLY_CASES))
 def test_shape_case_matches_fp64_restatement(backend, tag, gold):
     """The branching shapes (corr1d_config.py says which case reaches what) and, on the GPU, the production shape: every
     element against the restatement in fp64 (pinned to the reference's subsample above), d_ref the reference's stored number."""
@@ -211,10 +190,10 @@ def test_shape_case_matches_fp64_restatement(backend, tag, gold):
     outs, grads, _ = _product_case(env, tag)
     for i, k in ((0, "out_a"), (1, "out_b")):
         assert outs[i].shape == (B, out_channels(tag), H, W1) and outs[i].dtype == torch.float32 and outs[i].is_contiguous()
-        _check(outs[i], want[k], gold, f"{tag}:{k}", VALUE_FACTOR)
+        within(outs[i], want[k], float(gold[f"{tag}:{k}:dref"]), VALUE_FACTOR, f"{tag}:{k}")
     for k, g in grads.items():
-        _check(g, want[k], gold, f"{tag}:{k}", GRAD_FACTOR)
-    _check(_static_corr(env, tag), want["corr"], gold, f"{tag}:corr", VALUE_FACTOR)
+        within(g, want[k], float(gold[f"{tag}:{k}:dref"]), GRAD_FACTOR, f"{tag}:{k}")
+    within(_static_corr(env, tag), want["corr"], float(gold[f"{tag}:corr:dref"]), VALUE_FACTOR, f"{tag}:corr")
 
 
 # ------------------------------------------------------------------------------------------ behaviour
@@ -260,8 +239,7 @@ def _iterations(env, retain=False):
         outs = [fn(c.to(dev)) for c in coords]
         loss = sum((o * g.to(dev)).sum() for o, g in zip(outs, gws)) + (fn.corr_pyramid * _pack(wc).to(dev)).sum()
         loss.backward(retain_graph=retain)
-        if env.name == "hip":
-            torch.cuda.synchronize()
+        sync(env)
     return outs, (f1, f2), loss
 
 
@@ -271,9 +249,9 @@ def test_32_lookups_and_another_consumer_of_the_pyramid(env, gold):
     shared gradient buffer must reach the build node complete and be summed with the other consumer's gradient there."""
     want = _restated_iterations()
     outs, (f1, f2), _ = _iterations(env)
-    _check(torch.stack(outs), want["outs"], gold, f"{ITER}:outs", VALUE_FACTOR)
-    _check(f1.grad, want["g_fmap1"], gold, f"{ITER}:g_fmap1", GRAD_FACTOR)
-    _check(f2.grad, want["g_fmap2"], gold, f"{ITER}:g_fmap2", GRAD_FACTOR)
+    within(torch.stack(outs), want["outs"], float(gold[f"{ITER}:outs:dref"]), VALUE_FACTOR, f"{ITER}:outs")
+    within(f1.grad, want["g_fmap1"], float(gold[f"{ITER}:g_fmap1:dref"]), GRAD_FACTOR, f"{ITER}:g_fmap1")
+    within(f2.grad, want["g_fmap2"], float(gold[f"{ITER}:g_fmap2:dref"]), GRAD_FACTOR, f"{ITER}:g_fmap2")
 
 
 def test_second_backward_on_a_retained_graph_equals_the_first(env):
@@ -283,8 +261,7 @@ def test_second_backward_on_a_retained_graph_equals_the_first(env):
         t.grad = None
     with env.ctx():
         loss.backward()
-        if env.name == "hip":
-            torch.cuda.synchronize()
+        sync(env)
     assert all(torch.equal(a, t.grad) and a.abs().max().item() > 0 for a, t in zip(first, leaves))
 
 
@@ -372,7 +349,7 @@ def test_kernel_level_pyramid_and_lookup_at_wide(be, gold):  # noqa: F811
     cpyr = be.empty(n_c)
     be.call("stx_corr1d_pyramid_fwd", ptr(be.dev(f1)), ptr(be.dev(f2)), ptr(cpyr), B, Cf, H, W1, W2, L, scale)
     lv = [cpyr.cpu()[:cp[0].numel()].view(B, H, W1, W2)]
-    _check(lv[0].unsqueeze(3), _restated64(tag)["corr"], gold, f"{tag}:corr", VALUE_FACTOR)
+    within(lv[0].unsqueeze(3), _restated64(tag)["corr"], float(gold[f"{tag}:corr:dref"]), VALUE_FACTOR, f"{tag}:corr")
     for _ in range(L - 1):
         lv.append(pool(lv[-1]))
     assert [t.shape[-1] for t in lv] == [301, 150, 75, 37]
@@ -383,8 +360,8 @@ def test_kernel_level_pyramid_and_lookup_at_wide(be, gold):  # noqa: F811
     (_pack(pyramid(f164, f264, L)) * gc.double()).sum().backward()
     gf1, gf2 = be.empty(B, Cf, H, W1), be.empty(B, Cf, H, W2)
     be.call("stx_corr1d_pyramid_bwd", ptr(be.dev(gc)), ptr(be.dev(f1)), ptr(be.dev(f2)), ptr(gf1), ptr(gf2), B, Cf, H, W1, W2, L, scale)
-    _near(gf1, f164.grad, W2 * EPS, "pyramid backward fmap1")
-    _near(gf2, f264.grad, W1 * EPS, "pyramid backward fmap2")
+    near(gf1, f164.grad, W2 * EPS, "pyramid backward fmap1")
+    near(gf2, f264.grad, W1 * EPS, "pyramid backward fmap2")
     only1, only2 = be.empty(B, Cf, H, W1), be.empty(B, Cf, H, W2)
     be.call("stx_corr1d_pyramid_bwd", ptr(be.dev(gc)), ptr(be.dev(f1)), ptr(be.dev(f2)), ptr(only1), None, B, Cf, H, W1, W2, L, scale)
     be.call("stx_corr1d_pyramid_bwd", ptr(be.dev(gc)), ptr(be.dev(f1)), ptr(be.dev(f2)), None, ptr(only2), B, Cf, H, W1, W2, L, scale)
@@ -397,11 +374,11 @@ def test_kernel_level_pyramid_and_lookup_at_wide(be, gold):  # noqa: F811
     cp64 = [c.double().requires_grad_() for c in cp]
     o64 = raft_lookup(cp64, pos[0].double(), r)
     o64.backward(gws[0].double())
-    _near(out, o64, 8 * EPS, "lookup forward")
+    near(out, o64, 8 * EPS, "lookup forward")
     gcp = be.empty(n_c, fill=0.0)
     for _ in range(2):
         be.call("stx_corr1d_lookup_bwd", ptr(be.dev(gws[0])), ptr(be.dev(base)), None, jobs, nj, ptr(gcp), B, H, W1, W2, L)
-    _near(gcp, 2 * _pack([c.grad for c in cp64]), 8 * EPS, "lookup backward")
+    near(gcp, 2 * _pack([c.grad for c in cp64]), 8 * EPS, "lookup backward")
     # refused, nothing launched: five levels, nine jobs, radius 9, a job on a level the pyramid does not have
     from stereo_toolbox_amd import ops
     untouched = be.empty(B, out_channels(tag), H, W1)

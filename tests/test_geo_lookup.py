@@ -3,12 +3,12 @@ upsampling (`context_upsample`, models/IGEVStereo/submodule.py:243-255) on the k
 
 * tests/golden/geo_lookup.npz holds what the reference's OWN classes give on the seeded cases of tests/golden/geo_config.py, in
   fp32 and in fp64, and per tensor d_ref = max|fp32 - fp64| (tests/golden/make_golden_geo.py).
-* A plain-torch restatement of geometry.py in gather form (no grid_sample) lives in this file and is pinned to the fixture on
-  the CPU first -- in fp64 to 1e-11 (the reading of the reference), in fp32 to 2 x d_ref (two fp32 evaluations of one
-  quantity) -- so the fixture and the restatement check each other.
+* A plain-torch restatement of geometry.py in gather form (no grid_sample) lives in tests/restated.py and is pinned to the
+  fixture on the CPU first -- in fp64 to 1e-11 (the reading of the reference), in fp32 to 2 x d_ref (two fp32 evaluations of
+  one quantity; tests/parity.pin) -- so the fixture and the restatement check each other.
 * The product (emulator build here, gfx950 with `-m gpu`) is compared with the fp64 fixture: values within 2 x d_ref,
-  gradients within GRAD_FACTOR (3) x d_ref; where d_ref is zero the floor 2e-7 * max(1, max|want|) applies.  Every element of
-  every tensor of every case is compared.
+  gradients within GRAD_FACTOR (3) x d_ref; where d_ref is zero the floor 2e-7 * max(1, max|want|) applies
+  (tests/parity.within).  Every element of every tensor of every case is compared.
 * Tolerances against the restatement where no fixture exists (kernel-level pyramid gradients, the end-to-end chain):
   a sample is (1 - f) a + f b -- a handful of fp32 roundings on quantities of the tensor's scale, bounded here by
   8 * 2^-24 of the tensor's max -- plus, for the correlation samples, the rounding of `coords - disp` (half an ulp of the
@@ -22,16 +22,10 @@ import torch
 
 from tests.backends import be, ptr  # noqa: F401
 from tests.golden.geo_config import CASES, UPSAMPLE_CASES, inputs, out_channels, upsample_inputs
-from tests.test_models import GRAD_FACTOR, Env
+from tests.parity import EPS, GRAD_FACTOR, VALUE_FACTOR, env, near, pin_fixture, within_fixture  # noqa: F401
+from tests.restated import _pack, lookup, pool, pyramids, upsample
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geo_lookup.npz")
-VALUE_FACTOR = 2.0
-EPS = 2.0 ** -24
-
-
-@pytest.fixture(params=["emu", pytest.param("hip", marks=pytest.mark.gpu)])
-def env(request):
-    return Env(request.param)
 
 
 @pytest.fixture(scope="module")
@@ -39,79 +33,7 @@ def gold():
     return np.load(GOLD)
 
 
-def _within(got, gold, key, factor, what):
-    """|got - fp64 fixture| <= factor * d_ref (floor 2e-7 * max(1, max|want|) where d_ref is zero), over the whole tensor."""
-    want = torch.from_numpy(gold[key + ":f64"])
-    dref = float(gold[key + ":dref"])
-    got = got.detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    tol = factor * dref if dref > 0 else 2e-7 * max(1.0, want.abs().max().item())
-    print(f"{what}: err {err:.3e}  d_ref {dref:.3e}  ratio {err / dref if dref else float('nan'):.2f}")
-    assert err <= tol, (what, err, dref)
-
-
-def _near(got, want, rel, what):
-    want = want.detach().cpu().double()
-    got = got.detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    assert err <= rel * max(1.0, want.abs().max().item()), (what, err)
-
-
-# ------------------------------------------------------------------------------------------ the restatement (plain torch)
-def pool(x):
-    """avg_pool2d(x, [1, 2], stride=[1, 2]) along the last axis: pairs (2j, 2j+1), an odd tail dropped."""
-    n = x.shape[-1] // 2
-    return (x[..., 0:2 * n:2] + x[..., 1:2 * n:2]) / 2
-
-
-def pyramids(geo, f1, f2, levels):
-    """geo [B,C,D,H,W], f1 [B,Cf,H,W], f2 [B,Cf,H,W2] -> ([B,H,W,C,D_i]), ([B,H,W,W2_i])"""
-    gp = [geo.permute(0, 3, 4, 1, 2)]
-    cp = [torch.einsum("aijk,aijh->ajkh", f1, f2)]
-    for _ in range(levels - 1):
-        gp.append(pool(gp[-1]))
-        cp.append(pool(cp[-1]))
-    return gp, cp
-
-
-def sample(rows, x):
-    """rows [..., n], x [..., K] positions -> linear interpolation between floor(x) and floor(x) + 1, zero outside [0, n-1]."""
-    n = rows.shape[-1]
-    x0 = torch.floor(x)
-    f = x - x0
-    i0 = x0.long()
-
-    def tap(i):
-        ok = (i >= 0) & (i < n)
-        return torch.gather(rows, -1, i.clamp(0, n - 1)) * ok.to(rows.dtype)
-    return (1 - f) * tap(i0) + f * tap(i0 + 1)
-
-
-def lookup(gp, cp, disp, coords, radius):
-    B, _, H, W = disp.shape
-    dx = torch.arange(-radius, radius + 1, dtype=disp.dtype, device=disp.device)
-    d, c = disp.reshape(B, H, W, 1), coords.reshape(B, H, W, 1)
-    out = []
-    for i, (g, r) in enumerate(zip(gp, cp)):
-        C = g.shape[3]
-        xg = (d / 2 ** i + dx).unsqueeze(3).expand(B, H, W, C, 2 * radius + 1)
-        out.append(sample(g, xg).reshape(B, H, W, -1))
-        out.append(sample(r, c / 2 ** i - d / 2 ** i + dx))
-    return torch.cat(out, dim=-1).permute(0, 3, 1, 2).contiguous()
-
-
-def upsample(disp_low, wts):
-    B, _, h, w = disp_low.shape
-    p = torch.nn.functional.pad(disp_low[:, 0], (1, 1, 1, 1))
-    out = 0
-    for t in range(9):
-        tap = p[:, t // 3:t // 3 + h, t % 3:t % 3 + w]
-        out = out + wts[:, t] * tap.repeat_interleave(4, 1).repeat_interleave(4, 2)
-    return out
-
-
+# ------------------------------------------------------------------------------------------ the restatement vs the fixture
 def _restated_case(tag, dtype):
     B, C, D, H, W, W2, Cf, L, r = CASES[tag]
     geo, f1, f2, coords, disps, gws = inputs(tag)
@@ -127,27 +49,22 @@ def test_restatement_matches_reference_fixture(gold, tag):
     r64 = _restated_case(tag, torch.float64)
     r32 = _restated_case(tag, torch.float32)
     for k in r64:
-        want64 = torch.from_numpy(gold[f"{tag}:{k}:f64"])
-        assert r64[k].shape == want64.shape
-        assert (r64[k].detach() - want64).abs().max().item() <= 1e-11 * max(1.0, want64.abs().max().item()), k
-        want32 = torch.from_numpy(gold[f"{tag}:{k}:f32"])
-        assert r32[k].dtype == want32.dtype == torch.float32
-        dref = float(gold[f"{tag}:{k}:dref"])
-        assert dref > 0
-        assert (r32[k].detach() - want32).abs().max().item() <= 2 * dref, k
+        pin_fixture(r64[k], r32[k], gold, f"{tag}:{k}")
+
+
+def _restated_upsample(tag, dtype):
+    disp, wts, gw = upsample_inputs(tag)
+    disp, wts = disp.to(dtype).requires_grad_(), wts.to(dtype).requires_grad_()
+    out = upsample(disp, wts)
+    (out * gw.to(dtype)).sum().backward()
+    return {"out": out, "g_disp_low": disp.grad, "g_up_weights": wts.grad}
 
 
 @pytest.mark.parametrize("tag", list(UPSAMPLE_CASES))
 def test_upsample_restatement_matches_reference_fixture(gold, tag):
-    for dtype, suffix in ((torch.float64, "f64"), (torch.float32, "f32")):
-        disp, wts, gw = upsample_inputs(tag)
-        disp, wts = disp.to(dtype).requires_grad_(), wts.to(dtype).requires_grad_()
-        out = upsample(disp, wts)
-        (out * gw.to(dtype)).sum().backward()
-        for k, v in (("out", out), ("g_disp_low", disp.grad), ("g_up_weights", wts.grad)):
-            want = torch.from_numpy(gold[f"up_{tag}:{k}:{suffix}"])
-            tol = 1e-11 * max(1.0, want.abs().max().item()) if dtype == torch.float64 else 2 * float(gold[f"up_{tag}:{k}:dref"])
-            assert v.shape == want.shape and (v.detach() - want).abs().max().item() <= tol, (k, suffix)
+    r64, r32 = _restated_upsample(tag, torch.float64), _restated_upsample(tag, torch.float32)
+    for k in r64:
+        pin_fixture(r64[k], r32[k], gold, f"up_{tag}:{k}")
 
 
 # ------------------------------------------------------------------------------------------ the product vs the fp64 fixture
@@ -180,9 +97,9 @@ def test_lookup_matches_reference_fp64(env, gold, tag):
     for i, k in ((0, "out_a"), (1, "out_b")):
         o = outs[i]
         assert o.shape == (B, out_channels(tag), H, W) and o.dtype == torch.float32 and o.is_contiguous()
-        _within(o, gold, f"{tag}:{k}", VALUE_FACTOR, f"{tag} {k}")
+        within_fixture(o, gold, f"{tag}:{k}", VALUE_FACTOR, f"{tag} {k}")
     for k, g in grads.items():
-        _within(g, gold, f"{tag}:{k}", GRAD_FACTOR, f"{tag} {k}")
+        within_fixture(g, gold, f"{tag}:{k}", GRAD_FACTOR, f"{tag} {k}")
 
 
 @pytest.mark.parametrize("tag", list(CASES))
@@ -193,7 +110,7 @@ def test_corr_matches_reference_einsum(env, gold, tag):
     with env.ctx():
         corr = Combined_Geo_Encoding_Volume.corr(f1.to(env.device), f2.to(env.device))
     assert corr.shape == (B, H, W, 1, W2) and corr.dtype == torch.float32 and corr.is_contiguous()
-    _within(corr, gold, f"{tag}:corr", VALUE_FACTOR, f"{tag} corr")
+    within_fixture(corr, gold, f"{tag}:corr", VALUE_FACTOR, f"{tag} corr")
 
 
 @pytest.mark.parametrize("tag", list(UPSAMPLE_CASES))
@@ -206,17 +123,12 @@ def test_context_upsample_matches_reference_fp64(env, gold, tag):
         out = context_upsample(disp, wts)
         (out * gw.to(env.device)).sum().backward()
     assert out.shape == (B, 4 * h, 4 * w) and out.dtype == torch.float32 and out.is_contiguous()
-    _within(out, gold, f"up_{tag}:out", VALUE_FACTOR, "upsampled disparity")
-    _within(disp.grad, gold, f"up_{tag}:g_disp_low", GRAD_FACTOR, "g disp_low")
-    _within(wts.grad, gold, f"up_{tag}:g_up_weights", GRAD_FACTOR, "g up_weights")
+    within_fixture(out, gold, f"up_{tag}:out", VALUE_FACTOR, "upsampled disparity")
+    within_fixture(disp.grad, gold, f"up_{tag}:g_disp_low", GRAD_FACTOR, "g disp_low")
+    within_fixture(wts.grad, gold, f"up_{tag}:g_up_weights", GRAD_FACTOR, "g up_weights")
 
 
 # ------------------------------------------------------------------------------------------ kernel level (C-ABI)
-def _pack(levels_list):
-    """pixel-major levels ([rows..., len_i(, C)]) -> the flat pyramid buffer of include/stx_hip.h"""
-    return torch.cat([t.reshape(-1) for t in levels_list])
-
-
 def test_kernel_level_pyramids_and_lookup(be, gold):  # noqa: F811
     """stx_geo_pyramid_fwd/_bwd, stx_geo_corr_fwd/_bwd, stx_geo_lookup_fwd/_bwd through the C-ABI at the ragged case (odd D, odd
     W2, W = 18, B = 2, three levels)."""
@@ -236,13 +148,13 @@ def test_kernel_level_pyramids_and_lookup(be, gold):  # noqa: F811
     cpyr = be.empty(n_c)
     be.call("stx_geo_corr_fwd", ptr(be.dev(f1)), ptr(be.dev(f2)), ptr(cpyr), B, Cf, H, W, W2, L)
     lv0 = cpyr.cpu()[:cp[0].numel()].view(B, H, W, W2)
-    _within(lv0.unsqueeze(3), gold, f"{tag}:corr", VALUE_FACTOR, "corr level 0")
+    within_fixture(lv0.unsqueeze(3), gold, f"{tag}:corr", VALUE_FACTOR, "corr level 0")
     assert torch.equal(cpyr.cpu(), _pack([lv0, pool(lv0), pool(pool(lv0))]))
     # lookup forward on pyramids packed from the restatement
     out = be.empty(B, out_channels(tag), H, W)
     be.call("stx_geo_lookup_fwd", ptr(be.dev(_pack(gp))), ptr(be.dev(_pack(cp))), ptr(be.dev(disps[0])), ptr(be.dev(coords)), ptr(out),
             B, H, W, D, C, W2, L, r)
-    _within(out, gold, f"{tag}:out_a", VALUE_FACTOR, "lookup forward")
+    within_fixture(out, gold, f"{tag}:out_a", VALUE_FACTOR, "lookup forward")
     # lookup backward: ADDS into the buffers (twice -> twice the gradient), against autograd of the fp64 restatement
     gp64 = [g.double().requires_grad_() for g in gp]
     cp64 = [c.double().requires_grad_() for c in cp]
@@ -252,8 +164,8 @@ def test_kernel_level_pyramids_and_lookup(be, gold):  # noqa: F811
     for _ in range(2):
         be.call("stx_geo_lookup_bwd", ptr(be.dev(gws[0])), ptr(be.dev(disps[0])), ptr(be.dev(coords)), ptr(ggp), ptr(gcp),
                 B, H, W, D, C, W2, L, r)
-    _near(ggp, 2 * _pack([g.grad for g in gp64]), 8 * EPS, "lookup backward, geometry pyramid")
-    _near(gcp, 2 * _pack([c.grad for c in cp64]), 8 * EPS + W * 2 * EPS, "lookup backward, correlation pyramid")
+    near(ggp, 2 * _pack([g.grad for g in gp64]), 8 * EPS, "lookup backward, geometry pyramid")
+    near(gcp, 2 * _pack([c.grad for c in cp64]), 8 * EPS + W * 2 * EPS, "lookup backward, correlation pyramid")
     # pyramid backward kernels on a seeded pyramid gradient, against autograd of the restatement
     from stereo_toolbox_amd.utils import synthetic_tensor
     gg, gc = synthetic_tensor((n_g,), 901), synthetic_tensor((n_c,), 902)
@@ -263,10 +175,10 @@ def test_kernel_level_pyramids_and_lookup(be, gold):  # noqa: F811
     gvol, gf1, gf2 = be.empty(B, D, H, W, C), be.empty(B, Cf, H, W), be.empty(B, Cf, H, W2)
     be.call("stx_geo_pyramid_bwd", ptr(be.dev(gg)), ptr(gvol), B, D, H, W, C, L)
     be.call("stx_geo_corr_bwd", ptr(be.dev(gc)), ptr(be.dev(f1)), ptr(be.dev(f2)), ptr(gf1), ptr(gf2), B, Cf, H, W, W2, L)
-    _near(gvol.permute(0, 4, 1, 2, 3), geo64.grad, 8 * EPS, "pyramid backward")
+    near(gvol.permute(0, 4, 1, 2, 3), geo64.grad, 8 * EPS, "pyramid backward")
     # a dot product over W (W2) terms of size max|g| * max|f|: sqrt-free bound n * 2^-24 of the result's scale
-    _near(gf1, f164.grad, W2 * EPS, "corr backward fmap1")
-    _near(gf2, f264.grad, W * EPS, "corr backward fmap2")
+    near(gf1, f164.grad, W2 * EPS, "corr backward fmap1")
+    near(gf2, f264.grad, W * EPS, "corr backward fmap2")
 
 
 def test_kernel_level_context_upsample(be, gold):  # noqa: F811
@@ -276,9 +188,9 @@ def test_kernel_level_context_upsample(be, gold):  # noqa: F811
     out, gd, gwt = be.empty(B, 4 * h, 4 * w), be.empty(B, 1, h, w), be.empty(B, 9, 4 * h, 4 * w)
     be.call("stx_context_upsample_fwd", ptr(be.dev(disp)), ptr(be.dev(wts)), ptr(out), B, h, w)
     be.call("stx_context_upsample_bwd", ptr(be.dev(gw)), ptr(be.dev(disp)), ptr(be.dev(wts)), ptr(gd), ptr(gwt), B, h, w)
-    _within(out, gold, f"up_{tag}:out", VALUE_FACTOR, "upsample forward")
-    _within(gd, gold, f"up_{tag}:g_disp_low", GRAD_FACTOR, "upsample g disp")
-    _within(gwt, gold, f"up_{tag}:g_up_weights", GRAD_FACTOR, "upsample g weights")
+    within_fixture(out, gold, f"up_{tag}:out", VALUE_FACTOR, "upsample forward")
+    within_fixture(gd, gold, f"up_{tag}:g_disp_low", GRAD_FACTOR, "upsample g disp")
+    within_fixture(gwt, gold, f"up_{tag}:g_up_weights", GRAD_FACTOR, "upsample g weights")
 
 
 # ------------------------------------------------------------------------------------------ behaviour
@@ -367,12 +279,12 @@ def test_aggregation_to_lookup_to_upsample_end_to_end(env):
     (sum((o * g.cpu().double()).sum() for o, g in zip(outs64, gws)) + (up64 * gup.cpu().double()).sum()).backward()
     val = 8 * EPS + W4 * 2 * EPS
     for o, o64 in zip(outs, outs64):
-        _near(o, o64, val, "lookup values")
-    _near(up, up64, 16 * EPS, "upsampled disparity")                      # 9 products and their sum
-    _near(geo_in.grad, g64.grad, 2 * 8 * EPS, "g geo_encoding_volume")     # two lookups' contributions
-    _near(disp_in.grad, d64.grad, 144 * EPS, "g init_disp")               # 144-term sum per low-resolution pixel
-    _near(mli.grad, l64.grad, 2 * (8 * EPS + W4 * 2 * EPS) + W4 * EPS, "g match_left")
-    _near(mri.grad, r64.grad, 2 * (8 * EPS + W4 * 2 * EPS) + W4 * EPS, "g match_right")
+        near(o, o64, val, "lookup values")
+    near(up, up64, 16 * EPS, "upsampled disparity")                      # 9 products and their sum
+    near(geo_in.grad, g64.grad, 2 * 8 * EPS, "g geo_encoding_volume")     # two lookups' contributions
+    near(disp_in.grad, d64.grad, 144 * EPS, "g init_disp")               # 144-term sum per low-resolution pixel
+    near(mli.grad, l64.grad, 2 * (8 * EPS + W4 * 2 * EPS) + W4 * EPS, "g match_left")
+    near(mri.grad, r64.grad, 2 * (8 * EPS + W4 * 2 * EPS) + W4 * EPS, "g match_right")
     grads = [p.grad for p in m.parameters()]
     assert all(g is not None and torch.isfinite(g).all() for g in grads)
     assert sum(float(g.abs().sum()) for g in grads) > 0

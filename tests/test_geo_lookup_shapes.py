@@ -9,8 +9,8 @@ than one channel quad layout (C = 12, 16), lookup grids beyond a handful of work
 What a case is compared with.  Whole tensors of these sizes are not kept in git.  tests/golden/geo_lookup_shapes.npz
 (tests/golden/make_golden_geo.py, the reference's own classes in fp32 and fp64) keeps per tensor d_ref = max|fp32 - fp64| of the
 REFERENCE, max|fp64| and a strided subsample of the fp64 tensor.
- (a) the fp64 restatement of tests/test_geo_lookup.py (`pyramids`, `lookup`, `upsample`) is pinned to that subsample to 1e-11 of
-     the tensor's max -- the rule of test_restatement_matches_reference_fixture;
+ (a) the fp64 restatement of tests/restated.py (`pyramids`, `lookup`, `upsample`) is pinned to that subsample to 1e-11 of
+     the tensor's max -- tests/parity.pin_subsample;
  (b) EVERY element of the product's outputs and of all three gradients is compared with the restatement evaluated in fp64 at test
      time, within VALUE_FACTOR (2) x d_ref for values and GRAD_FACTOR (3) x d_ref for gradients -- d_ref being the stored number.
 The kernel-level entry points get the wide and deep cases through the C-ABI with the checks that are exact today (geometry
@@ -30,8 +30,8 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.geo_config import (EXTRA_CALLS, GPU_ONLY_SHAPE_CASES, GPU_ONLY_SHAPE_UPSAMPLE_CASES, ITER_CALLS, ITER_CASE,
                                      REFUSED_PYRAMID, SHAPE_CASES, SHAPE_UPSAMPLE_CASES, SUBSAMPLE, iter_inputs, shape_inputs,
                                      shape_out_channels, shape_upsample_inputs, subsample)
-from tests.test_geo_lookup import EPS, VALUE_FACTOR, _near, _pack, _within, env, lookup, pool, pyramids, upsample  # noqa: F401
-from tests.test_models import GRAD_FACTOR, Env
+from tests.parity import EPS, GRAD_FACTOR, VALUE_FACTOR, Env, env, near, on, pin_subsample, sync, within  # noqa: F401
+from tests.restated import _pack, lookup, pool, pyramids, upsample
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geo_lookup_shapes.npz")
 
@@ -41,28 +41,19 @@ def gold():
     return np.load(GOLD)
 
 
-def _on(tags, gpu_only):
-    """(backend, tag): every case on the GPU, on the emulator all but the gpu-only ones."""
-    return [("emu", t) for t in tags if t not in gpu_only] + [pytest.param("hip", t, marks=pytest.mark.gpu) for t in tags]
-
-
 def _check(got, want64, gold, key, factor, log):
-    """Every element of `got` against the fp64 restatement, within factor x the reference's stored d_ref (`_within`)."""
+    """Every element of `got` against the fp64 restatement, within factor x the reference's stored d_ref; the achieved ratio
+    goes into `log` under the tensor's name."""
     dref = float(gold[key + ":dref"])
     assert dref > 0, key
-    _within(got, {key + ":f64": want64.detach().numpy(), key + ":dref": dref}, key, factor, key)
-    log[key.split(":")[1]] = round((got.detach().cpu().double() - want64.detach()).abs().max().item() / dref, 3)
+    within(got, want64, dref, factor, key, lambda what, ratio, **_: log.update({key.split(":")[1]: round(ratio, 3)}))
 
 
 def _pinned(r64, gold, tag):
     """(a): the restatement against the stored subsample of the reference's fp64 tensors."""
     for k, v in r64.items():
-        want = torch.from_numpy(gold[f"{tag}:{k}:sub"])
-        peak = float(gold[f"{tag}:{k}:max"])
-        got = subsample(v.detach())
-        assert got.shape == want.shape and want.numel() >= min(v.numel(), SUBSAMPLE), (tag, k, got.shape, want.shape)
-        assert abs(v.detach().abs().max().item() - peak) <= 1e-11 * max(1.0, peak), (tag, k)
-        assert (got - want).abs().max().item() <= 1e-11 * max(1.0, peak), (tag, k)
+        pin_subsample(v, torch.from_numpy(gold[f"{tag}:{k}:sub"]), float(gold[f"{tag}:{k}:max"]), subsample, min(v.numel(), SUBSAMPLE),
+                      f"{tag}:{k}")
 
 
 # ------------------------------------------------------------------------------------------ the restatement, fp64, at test time
@@ -121,7 +112,7 @@ def test_upsample_restatement_matches_reference_subsample(gold, tag):
 
 
 # ------------------------------------------------------------------------------------------ (b) the product at these shapes
-@pytest.mark.parametrize("backend,tag", _on(SHAPE_CASES, GPU_ONLY_SHAPE_CASES))
+@pytest.mark.parametrize("backend,tag", on(SHAPE_CASES, GPU_ONLY_SHAPE_CASES))
 def test_shape_case_matches_fp64_restatement(backend, tag, gold, parity_log):
     from stereo_toolbox_amd.models.IGEVStereo import Combined_Geo_Encoding_Volume
     env = Env(backend)
@@ -137,8 +128,7 @@ def test_shape_case_matches_fp64_restatement(backend, tag, gold, parity_log):
         outs = [fn(d.to(dev), coords.to(dev)) for d in disps]
         sum((o * g.to(dev)).sum() for o, g in zip(outs, gws)).backward()
         corr = Combined_Geo_Encoding_Volume.corr(f1.detach(), f2.detach())
-        if backend == "hip":
-            torch.cuda.synchronize()
+        sync(env)
     wall = time.time() - t0
     log = {}
     for k, o in (("out_a", outs[0]), ("out_b", outs[1])):
@@ -195,12 +185,12 @@ def test_kernel_level_pyramids_at_branching_shapes(be, gold, tag):  # noqa: F811
     o64 = lookup([g.permute(0, 1, 2, 4, 3) for g in gp64], cp64, disps[0].double(), coords.double(), r)
     o64.backward(gws[0].double())
     reach = max(W2, float(coords.max()) + 1)                             # the magnitude `coords - disp` is rounded at
-    _near(out, o64, 8 * EPS + reach * 2 * EPS, "lookup forward")
+    near(out, o64, 8 * EPS + reach * 2 * EPS, "lookup forward")
     ggp, gcp = be.empty(n_g, fill=0.0), be.empty(n_c, fill=0.0)
     be.call("stx_geo_lookup_bwd", ptr(be.dev(gws[0])), ptr(be.dev(disps[0])), ptr(be.dev(coords)), ptr(ggp), ptr(gcp),
             B, H, W, D, C, W2, L, r)
-    _near(ggp, _pack([g.grad for g in gp64]), 8 * EPS, "lookup backward, geometry pyramid")
-    _near(gcp, _pack([c.grad for c in cp64]), 8 * EPS + reach * 2 * EPS, "lookup backward, correlation pyramid")
+    near(ggp, _pack([g.grad for g in gp64]), 8 * EPS, "lookup backward, geometry pyramid")
+    near(gcp, _pack([c.grad for c in cp64]), 8 * EPS + reach * 2 * EPS, "lookup backward, correlation pyramid")
     # pyramid backward kernels on a seeded gradient of EVERY pyramid element, against autograd of the restatement
     gg, gc = synthetic_tensor((n_g,), 911), synthetic_tensor((n_c,), 912)
     geo64, f164, f264 = (t.double().requires_grad_() for t in (geo, f1, f2))
@@ -209,10 +199,10 @@ def test_kernel_level_pyramids_at_branching_shapes(be, gold, tag):  # noqa: F811
     gvol, gf1, gf2 = be.empty(B, D, H, W, C), be.empty(B, Cf, H, W), be.empty(B, Cf, H, W2)
     be.call("stx_geo_pyramid_bwd", ptr(be.dev(gg)), ptr(gvol), B, D, H, W, C, L)
     be.call("stx_geo_corr_bwd", ptr(be.dev(gc)), ptr(be.dev(f1)), ptr(be.dev(f2)), ptr(gf1), ptr(gf2), B, Cf, H, W, W2, L)
-    _near(gvol.permute(0, 4, 1, 2, 3), geo64.grad, 8 * EPS, "pyramid backward")
+    near(gvol.permute(0, 4, 1, 2, 3), geo64.grad, 8 * EPS, "pyramid backward")
     # a dot product over W2 (W) terms of size max|g| * max|f|: n * 2^-24 of the result's scale
-    _near(gf1, f164.grad, W2 * EPS, "corr backward fmap1")
-    _near(gf2, f264.grad, W * EPS, "corr backward fmap2")
+    near(gf1, f164.grad, W2 * EPS, "corr backward fmap1")
+    near(gf2, f264.grad, W * EPS, "corr backward fmap2")
     # one gradient only: the other launch is left out, the result is the same bits
     only1, only2 = be.empty(B, Cf, H, W), be.empty(B, Cf, H, W2)
     be.call("stx_geo_corr_bwd", ptr(be.dev(gc)), ptr(be.dev(f1)), ptr(be.dev(f2)), ptr(only1), None, B, Cf, H, W, W2, L)
@@ -268,8 +258,7 @@ class _Run:
     def backward(self, **kw):
         with self.env.ctx():
             self.loss.backward(**kw)
-            if self.env.name == "hip":
-                torch.cuda.synchronize()
+            sync(self.env)
 
     @property
     def grads(self):
@@ -327,8 +316,7 @@ def test_two_objects_alive_at_once_keep_their_own_gradients(env):
         for i in range(6):
             loss = loss + (fns[i % 2](disps[i].to(dev), coords.to(dev)) * gws[i].to(dev)).sum()
         loss.backward()
-        if env.name == "hip":
-            torch.cuda.synchronize()
+        sync(env)
     for lv, want in zip(leaves, apart):
         _same_bits({k: t.grad for k, t in zip(("g_geo", "g_fmap1", "g_fmap2"), lv)}, want)
     assert not torch.equal(leaves[0][0].grad, leaves[1][0].grad)
@@ -430,7 +418,7 @@ def test_low_precision_feature_maps_outside_autocast_are_refused():
 
 
 # ------------------------------------------------------------------------------------------ context_upsample
-@pytest.mark.parametrize("backend,tag", _on(SHAPE_UPSAMPLE_CASES, GPU_ONLY_SHAPE_UPSAMPLE_CASES))
+@pytest.mark.parametrize("backend,tag", on(SHAPE_UPSAMPLE_CASES, GPU_ONLY_SHAPE_UPSAMPLE_CASES))
 def test_context_upsample_at_larger_shapes(backend, tag, gold, parity_log):
     """More than 256 low-resolution pixels per image and B = 2 (a second workgroup of context_upsample_bwd_disp_kernel, a batch
     boundary inside one), and 144x240 on the GPU."""
@@ -444,8 +432,7 @@ def test_context_upsample_at_larger_shapes(backend, tag, gold, parity_log):
     with env.ctx():
         out = context_upsample(disp, wts)
         (out * gw.to(env.device)).sum().backward()
-        if backend == "hip":
-            torch.cuda.synchronize()
+        sync(env)
     wall = time.time() - t0
     assert out.shape == (B, 4 * h, 4 * w) and out.dtype == torch.float32 and out.is_contiguous()
     log = {}

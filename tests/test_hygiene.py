@@ -13,8 +13,8 @@ import pytest
 import torch
 import torch.nn as nn
 
-from tests.backends import be, ndhwc, ptr  # noqa: F401
-from tests.test_kernels import pack
+from tests.backends import be, ndhwc, pack, ptr  # noqa: F401
+from tests.parity import directional
 
 
 def _twice(be, fn, outs_fn):
@@ -118,29 +118,6 @@ def test_run_to_run_bitwise_reproducibility(be):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _directional(fn, inputs, eps=3e-3, tol=3e-2, seed=0):
-    """fn(*inputs) -> tensor (or list of tensors).  Checks <grad_i, v_i> against the central difference for every input."""
-    g = torch.Generator().manual_seed(seed)
-
-    def flat(y):
-        return torch.cat([t.reshape(-1) for t in y]) if isinstance(y, (list, tuple)) else y.reshape(-1)
-
-    xs = [t.clone().requires_grad_() for t in inputs]
-    y = flat(fn(*xs))
-    gy = torch.randn(y.shape, generator=g)
-    (y * gy).sum().backward()
-    for i, x in enumerate(xs):
-        v = torch.randn(x.shape, generator=g)
-        v *= float(x.detach().abs().mean()) / (v.norm() / (x.numel() ** 0.5))     # step relative to the input's magnitude
-        with torch.no_grad():
-            args_p = [t.detach() + (eps * v if j == i else 0) for j, t in enumerate(inputs)]
-            args_m = [t.detach() - (eps * v if j == i else 0) for j, t in enumerate(inputs)]
-            fd = ((flat(fn(*args_p)).double() - flat(fn(*args_m)).double()) * gy.double()).sum().item() / (2 * eps)
-        an = (x.grad.double() * v.double()).sum().item()
-        scale = max(abs(an), abs(fd), 1e-3 * (x.grad.norm().item() * v.norm().item()))
-        assert abs(an - fd) <= tol * scale, f"input {i}: analytic {an:.6e} vs finite difference {fd:.6e}"
-
-
 def test_finite_difference_gradients():
     from stereo_toolbox_amd import ops
     from stereo_toolbox_amd.aggregation import conv_block
@@ -150,30 +127,30 @@ def test_finite_difference_gradients():
         # builders (bilinear in the gwc features, linear in the concat features), both concat semantics
         Lg, Rg, Lc, Rc = torch.randn(1, 16, 2, 19), torch.randn(1, 16, 2, 19), torch.randn(1, 4, 2, 19), torch.randn(1, 4, 2, 19)
         for ml in (True, False):
-            _directional(lambda a, b, c, d: ops.cost_volume(a, b, c, d, 6, 4, mask_left=ml), [Lg, Rg, Lc, Rc], seed=1)
+            directional(lambda a, b, c, d: ops.cost_volume(a, b, c, d, 6, 4, mask_left=ml), [Lg, Rg, Lc, Rc], seed=1)
         # ACVNet attention-weighted concat volume
         prob = torch.softmax(torch.randn(1, 5, 2, 19), 1)
-        _directional(lambda a, b, p: ops.ac_volume(a, b, p, 5), [Lc, Rc, prob], seed=2)
+        directional(lambda a, b, p: ops.ac_volume(a, b, p, 5), [Lc, Rc, prob], seed=2)
         # CFNet cascade volume (features only; the integer samples carry no gradient)
         smp = torch.randint(-2, 9, (1, 3, 2, 19)).float()
-        _directional(lambda a, b, c, d: ops.sampled_volume(a, b, c, d, smp, 4), [Lg, Rg, Lc, Rc], seed=3)
+        directional(lambda a, b, c, d: ops.sampled_volume(a, b, c, d, smp, 4), [Lg, Rg, Lc, Rc], seed=3)
         # depth-wise patch convolution
         dil = torch.tensor([1, 2], dtype=torch.int32)
-        _directional(lambda x, w: ops.dwconv_hw(x, w, dil), [torch.randn(1, 2, 5, 9, 8), torch.randn(8, 9)], seed=4)
+        directional(lambda x, w: ops.dwconv_hw(x, w, dil), [torch.randn(1, 2, 5, 9, 8), torch.randn(8, 9)], seed=4)
         # conv / transposed conv / classifier tail + train-mode BatchNorm (+ReLU, residual, second branch), as blocks
         conv = nn.Conv3d(8, 8, 3, 1, 1, bias=False)
         bn = nn.BatchNorm3d(8).train()
         x = torch.randn(1, 3, 4, 9, 8)
         res = torch.randn(1, 3, 4, 9, 8)
-        _directional(lambda a, w: _block(conv_block, a, conv, bn, w, None, None, relu=True),
+        directional(lambda a, w: _block(conv_block, a, conv, bn, w, None, None, relu=True),
                      [x, conv.weight.detach().clone()], eps=3e-4, seed=5)   # (ReLU kinks: small step)
-        _directional(lambda a, w, g, b: _block(conv_block, a, conv, bn, w, g, b, relu=False),       # smooth: BN affine too
+        directional(lambda a, w, g, b: _block(conv_block, a, conv, bn, w, g, b, relu=False),       # smooth: BN affine too
                      [x, conv.weight.detach().clone(), torch.rand(8) + 0.5, torch.randn(8)], seed=16)
-        _directional(lambda a, r, w: _block(conv_block, a, conv, bn, w, None, None, relu=False, residual=r),
+        directional(lambda a, r, w: _block(conv_block, a, conv, bn, w, None, None, relu=False, residual=r),
                      [x, res, conv.weight.detach().clone()], seed=6)
         conv2 = nn.Conv3d(8, 32, 3, 2, 1, bias=False)
         bn2 = nn.BatchNorm3d(32).train()
-        _directional(lambda a, w: _block(conv_block, a, conv2, bn2, w, None, None, relu=True),
+        directional(lambda a, w: _block(conv_block, a, conv2, bn2, w, None, None, relu=True),
                      [torch.randn(1, 4, 4, 10, 8), conv2.weight.detach().clone()], eps=3e-4, seed=7)
         dc = nn.ConvTranspose3d(32, 8, 3, padding=1, output_padding=1, stride=2, bias=False)
         bnd = nn.BatchNorm3d(8).train()
@@ -188,17 +165,17 @@ def test_finite_difference_gradients():
             return conv_block(a, dc, bnd, relu=True, second=(f, redir, bnr))
         dc.weight.requires_grad_(False)
         redir.weight.requires_grad_(False)
-        _directional(lambda a, f: hour(a, f, dc.weight.data, redir.weight.data), [xs, xf], eps=3e-4, seed=8)
+        directional(lambda a, f: hour(a, f, dc.weight.data, redir.weight.data), [xs, xf], eps=3e-4, seed=8)
         c1 = nn.Conv3d(16, 1, 3, 1, 1, bias=False)
-        _directional(lambda a, w: _block(conv_block, a, c1, None, w, None, None), [torch.randn(1, 3, 4, 9, 16),
+        directional(lambda a, w: _block(conv_block, a, c1, None, w, None, None), [torch.randn(1, 3, 4, 9, 16),
                                                                                    c1.weight.detach().clone()], seed=9)
         # regression head (both interpolation rules), soft-argmax, Mish
         cost = torch.randn(1, 4, 5, 7) * 2
-        _directional(lambda c: ops.regression_head(c, 16, 20, 28), [cost], seed=10)
-        _directional(lambda c: ops.regression_head(c, 16, 20, 28, align_corners=True), [cost], seed=11)
+        directional(lambda c: ops.regression_head(c, 16, 20, 28), [cost], seed=10)
+        directional(lambda c: ops.regression_head(c, 16, 20, 28, align_corners=True), [cost], seed=11)
         p = torch.softmax(torch.randn(1, 12, 3, 5) * 2, 1)
-        _directional(lambda t: ops.softargmax(t, 12, True), [p], seed=12)
-        _directional(lambda t: ops.mish(t), [torch.randn(2, 3, 4, 8) * 2], seed=13)
+        directional(lambda t: ops.softargmax(t, 12, True), [p], seed=12)
+        directional(lambda t: ops.mish(t), [torch.randn(2, 3, 4, 8) * 2], seed=13)
         # (the modal estimators are piecewise: their mode support jumps under any finite step -- their backward kernel is
         #  checked against autograd through the oracle, whose gradients are pinned to the reference's: test_kernels.py)
 
@@ -279,6 +256,22 @@ def test_no_test_module_needs_the_reference_tree():
         "print('BAD', bad) if bad else print('OK')\n")
     r = subprocess.run([sys.executable, "-c", code, *mods], cwd=os.path.dirname(here), capture_output=True, text=True, timeout=600)
     assert r.stdout.strip().endswith("OK"), (r.stdout[-1500:], r.stderr[-1500:])
+
+
+def test_no_test_module_imports_another():
+    """What test modules share lives in tests/parity.py, tests/restated.py and tests/backends.py: importing a test module for a
+    helper drags its fixtures, its imports (the oracle) and its module-level work along, and hides which copy of a rule holds."""
+    import glob
+    import os
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    absolute = re.compile(r"^\s*(from|import)\s+tests\.test_")
+    relative = re.compile(r"^\s*from\s+\.+\s*(test_|import\s+(\w+\s*,\s*)*test_)")
+    bad = []
+    for path in sorted(glob.glob(os.path.join(here, "test_*.py"))):
+        with open(path) as f:
+            bad += [(os.path.basename(path), n, line.strip()) for n, line in enumerate(f, 1) if absolute.match(line) or relative.match(line)]
+    assert not bad, bad
 
 
 def test_no_build_baton_in_the_tree():

@@ -7,7 +7,6 @@
 * the drop-in modules (`BasicConv`, `FeatureAtt`, `hourglass`, `IGEVCostAggregation`) vs the oracle: eval, and a full
   train step with every parameter / input gradient and the BatchNorm running statistics; state-dict keys vs the reference's.
 """
-import contextlib
 import json
 import os
 
@@ -20,6 +19,7 @@ from oracle import torch_oracle as O
 from stereo_toolbox_amd.utils import fill_state_dict, synthetic_tensor
 from tests.backends import be, ndhwc, ptr  # noqa: F401
 from tests.golden.igev_agg_config import B, FEAT_CH, H4, MAXDISP, W4, fill
+from tests.parity import env  # noqa: F401
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -200,25 +200,6 @@ def test_leaky_relu_activation_code(be):
 
 
 # ------------------------------------------------------------------------------------------------ drop-in modules
-class Env:
-    def __init__(self, name):
-        self.name = name
-        if name == "hip" and not torch.cuda.is_available():
-            pytest.skip("no ROCm device")
-        self.device = torch.device("cuda:0" if name == "hip" else "cpu")
-
-    def ctx(self):
-        if self.name == "emu":
-            from tests.emu_util import emu_product_path
-            return emu_product_path()
-        return contextlib.nullcontext()
-
-
-@pytest.fixture(params=["emu", pytest.param("hip", marks=pytest.mark.gpu)])
-def env(request):
-    return Env(request.param)
-
-
 def test_basic_conv_deconv4_and_feature_att_modules(env):
     """BasicConv(deconv k4 s2 p1 + BN + LeakyReLU, train mode) and FeatureAtt (eval) as nn.Modules with the reference's
     call convention (NCDHW in / out), forward + backward vs the fixture produced by the reference's own classes."""

@@ -14,6 +14,7 @@ from oracle import torch_oracle as O
 from stereo_toolbox_amd.utils import synthetic_tensor
 from tests.backends import be, ptr  # noqa: F401
 from tests.golden.make_golden_igev import IMG_SHAPES, synthetic_image
+from tests.parity import Env
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "igev_preprocess.npz")
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -87,27 +88,12 @@ def test_prepare_pair_and_unpad_gpu():
     assert torch.equal(l2.cpu(), lo) and torch.equal(r2.cpu(), ro) and torch.equal(d2.cpu(), d) and torch.equal(m2.cpu(), m)
 
 
-class _Env:
-    def __init__(self, name):
-        self.name = name
-        if name == "hip" and not torch.cuda.is_available():
-            pytest.skip("no ROCm device")
-        self.device = torch.device("cuda:0" if name == "hip" else "cpu")
-
-    def ctx(self):
-        import contextlib
-        if self.name == "emu":
-            from tests.emu_util import emu_product_path
-            return emu_product_path()
-        return contextlib.nullcontext()
-
-
 @pytest.mark.parametrize("envname", ["emu", pytest.param("hip", marks=pytest.mark.gpu)])
 def test_igev_initial_volume_api(envname):
     """models.IGEVStereo: build_gwc_volume at 8 groups x 12 channels (igev_stereo.py:206) and the 1/4-resolution
     softmax + disparity_regression (igev_stereo.py:211-212), forward and backward, vs the oracle."""
     from stereo_toolbox_amd.models.IGEVStereo import init_disparity, init_gwc_volume
-    env = _Env(envname)
+    env = Env(envname)
     B, C, H4, W4, maxdisp = (1, 96, 3, 40, 64) if envname == "emu" else (2, 96, 80, 184, 192)
     ml, mr = synthetic_tensor((B, C, H4, W4), 61), synthetic_tensor((B, C, H4, W4), 62)
     gv = synthetic_tensor((B, 8, maxdisp // 4, H4, W4), 63)

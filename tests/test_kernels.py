@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import torch_oracle as O
-from tests.backends import be, ndhwc, ncdhw, ptr, tune  # noqa: F401
+from tests.backends import be, ndhwc, ncdhw, pack, ptr, tune  # noqa: F401
 
 
 def _close(got, ref, rtol=1e-4, atol=1e-5):
@@ -371,16 +371,6 @@ def test_modal_estimators_backward(be, case):
 
 
 # ------------------------------------------------------------------------------ convolutions
-def pack(be, w, mode):
-    A, Bd = w.shape[0], w.shape[1]
-    T = w[0, 0].numel()
-    K, N = (Bd, A) if mode == 0 else (A, Bd)
-    n = be.raw("stx_conv3d_packed_floats")(K, N, T)
-    wp = be.empty(n)
-    be.call("stx_conv3d_pack_weight", ptr(be.dev(w)), ptr(wp), A, Bd, T, mode)
-    return wp
-
-
 def run_conv(be, x, w, ks, stride, scale=None, bias=None, res=None, relu=0, stats=False, mode=0, cout=None):
     B, Cin, D, H, W = x.shape
     Cout = cout if cout is not None else w.shape[0]

@@ -5,37 +5,12 @@
 * hip  (`-m gpu`): the same modules on the real gfx950 library at 64x128 / 256x512.
 Tolerance on disparities: 1e-3 max-abs (BASELINE.json); gradients: 2e-3 of the tensor's max.
 """
-import contextlib
-
 import pytest
 import torch
 
 from oracle import torch_oracle as O
 from stereo_toolbox_amd.utils import fill_state_dict, synthetic_tensor
-
-LOSS_W = (0.5, 0.5, 0.7, 1.0)
-
-
-class Env:
-    def __init__(self, name):
-        self.name = name
-        if name == "hip":
-            if not torch.cuda.is_available():
-                pytest.skip("no ROCm device")
-            self.device = torch.device("cuda:0")
-        else:
-            self.device = torch.device("cpu")
-
-    def ctx(self):
-        if self.name == "emu":
-            from tests.emu_util import emu_product_path
-            return emu_product_path()
-        return contextlib.nullcontext()
-
-
-@pytest.fixture(params=["emu", pytest.param("hip", marks=pytest.mark.gpu)])
-def env(request):
-    return Env(request.param)
+from tests.parity import GRAD_FACTOR, LOSS_W, Env, env, filled  # noqa: F401
 
 
 @pytest.fixture
@@ -43,14 +18,6 @@ def emu_env():
     """Train-step tests that evaluate the oracle live (fp32 + fp64, tiny shapes): emulator only.  Their GPU twins compare with
     fixtures generated from the reference at a well-conditioned shape (test_*_toy_train_step_* below)."""
     return Env("emu")
-
-
-def _filled(ctor, *a, **k):
-    m = ctor(*a, **k)
-    sd = m.state_dict()
-    fill_state_dict(sd)
-    m.load_state_dict(sd)
-    return m, {k_: v.clone() for k_, v in sd.items()}
 
 
 def _shape(env):
@@ -64,7 +31,7 @@ def test_gwcnet_eval_parity(env, concat):
     H, W, D, B = _shape(env)
     if env.name == "emu" and not concat:
         pytest.skip("GwcNet_G differs from _GC only in the volume channels; covered on the GPU")
-    m, sd = _filled(GwcNet, D, concat)
+    m, sd = filled(GwcNet, D, concat)
     m = m.to(env.device).eval()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
     with env.ctx(), torch.no_grad():
@@ -76,7 +43,7 @@ def test_gwcnet_eval_parity(env, concat):
     assert (got - ref).abs().max().item() < 1e-3
 
 
-GRAD_FACTOR = 3.0     # product-vs-fp64 may be at most this many times the fp32 reference's own distance from fp64
+# (GRAD_FACTOR, the bound on gradients against fp64 that every family shares, lives in tests/parity.py)
 PRED_FACTOR = 1.5     # full-size train steps (achieved 0.5-0.7 x, profiles/r03_parity_report.jsonl)
 PRED_FACTOR_SMALL = 2.0   # small shapes (emulator runs, the 128x256 fixture tests)
 RTOL_GRAD = 6e-3      # floor of a gradient tolerance as a fraction of the tensor's max (hand-written tensors, GPU)
@@ -156,7 +123,7 @@ def test_gwcnet_gc_train_parity(emu_env, parity_log):
     from stereo_toolbox_amd.models import GwcNet_GC
     env = emu_env
     H, W, D, B = _shape(env)
-    m, sd = _filled(GwcNet_GC, D)
+    m, sd = filled(GwcNet_GC, D)
     m = m.to(env.device).train()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
     gt = synthetic_tensor((B, H, W), 3, lo=0.0, hi=float(D - 2))
@@ -397,7 +364,7 @@ def test_acvnet_train_grads_hand_written_path_isolated(emu_env, parity_log):
     env = emu_env
     H, W, D, B = 16, 64, 64, 1
     dev = env.device
-    m, sd = _filled(ACVNet, D)
+    m, sd = filled(ACVNet, D)
     m = m.to(dev).train()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
     gt = synthetic_tensor((B, H, W), 3, lo=0.0, hi=float(D - 2))
@@ -447,7 +414,7 @@ def test_acvnet_eval_parity(env, flags):
     H, W, D, B = _acv_shape(env)
     if env.name == "emu" and flags:
         pytest.skip("attention-only variant covered on the GPU")
-    m, sd = _filled(ACVNet, D, **flags)
+    m, sd = filled(ACVNet, D, **flags)
     m = m.to(env.device).eval()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
     with env.ctx(), torch.no_grad():
@@ -499,7 +466,7 @@ def test_psmnet_aggregation_parity(env):
     from stereo_toolbox_amd.models import PSMNet
     D = 32 if env.name == "emu" else 64
     h4, w4 = (8, 16) if env.name == "emu" else (16, 32)   # >= 16 voxels/channel at the 1/16 level for BN
-    m, sd = _filled(PSMNet, D)
+    m, sd = filled(PSMNet, D)
     m = m.to(env.device)
     fl, fr = synthetic_tensor((1, 32, h4, w4), 5), synthetic_tensor((1, 32, h4, w4), 6)
     m.eval()
@@ -528,7 +495,7 @@ def test_psmnet_aggregation_parity(env):
 def test_psmnet_config1_eval():
     """BASELINE.json configs[0]: PSMNet forward on one 256x512 pair, D=64 (minimum legal PSMNet input)."""
     from stereo_toolbox_amd.models import PSMNet
-    m, sd = _filled(PSMNet, 64)
+    m, sd = filled(PSMNet, 64)
     m = m.cuda().eval()
     left, right = synthetic_tensor((1, 3, 256, 512), 1), synthetic_tensor((1, 3, 256, 512), 2)
     with torch.no_grad():
@@ -767,7 +734,7 @@ def test_full_size_eval_parity(tag, parity_log):
     gold = _gold("fullsize_eval.npz")
     H, W = (int(v) for v in tag.split("_")[-1].split("x"))
     acv = tag.startswith("acv")
-    m, sd = _filled(ACVNet if acv else GwcNet_GC, 192)
+    m, sd = filled(ACVNet if acv else GwcNet_GC, 192)
     m = m.cuda().eval()
     left, right = synthetic_tensor((1, 3, H, W), 1), synthetic_tensor((1, 3, H, W), 2)
     rec = {}
@@ -827,7 +794,7 @@ def _full_size_train_step(ctor, gold_name, B, tag, parity_log, rm_module):
         pytest.skip("no ROCm device")
     gold = _gold(gold_name)
     H, W, D = 576, 960, 192
-    m, sd = _filled(ctor, D)
+    m, sd = filled(ctor, D)
     assert state_dict_digest(sd) == int(gold["digest"]), "filler weights differ from the fixture's"
     m = m.cuda().train()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
@@ -927,7 +894,7 @@ def test_eval_mode_with_autograd(env):
     BN, or input-gradient analyses: the autograd path must use the running stats and match the oracle."""
     from stereo_toolbox_amd.models import GwcNet_GC
     H, W, D, B = _shape(env)
-    m, sd = _filled(GwcNet_GC, D)
+    m, sd = filled(GwcNet_GC, D)
     m = m.to(env.device).eval()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
     with env.ctx():
@@ -953,7 +920,7 @@ def test_acvnet_frozen_attention_train(env):
     if env.name == "emu":
         pytest.skip("flag combination covered on the GPU (the default combination runs on the emulator)")
     H, W, D, B = _acv_shape(env)
-    m, sd = _filled(ACVNet, D, freeze_attn_weights=True)
+    m, sd = filled(ACVNet, D, freeze_attn_weights=True)
     m = m.to(env.device).train()
     left, right = synthetic_tensor((B, 3, H, W), 1), synthetic_tensor((B, 3, H, W), 2)
     with env.ctx():
@@ -977,7 +944,7 @@ def test_pcwnet_gc_eval_parity_emu():
     from tests.emu_util import emu_product_path
     from stereo_toolbox_amd.models.PCWNet import PCWNet_GC
     D = 64
-    m, sd = _filled(PCWNet_GC, D)
+    m, sd = filled(PCWNet_GC, D)
     m.eval()
     left, right = synthetic_tensor((1, 3, 32, 64), 1), synthetic_tensor((1, 3, 32, 64), 2)
     with torch.no_grad(), emu_product_path():
@@ -1034,7 +1001,7 @@ def test_pcwnet_hourglassup_train_emu():
 def test_pcwnet_gc_eval_parity_gpu():
     from stereo_toolbox_amd.models.PCWNet import PCWNet_GC
     D = 64
-    m, sd = _filled(PCWNet_GC, D)
+    m, sd = filled(PCWNet_GC, D)
     dev = torch.device("cuda:0")
     m = m.to(dev).eval()
     left, right = synthetic_tensor((2, 3, 64, 128), 1), synthetic_tensor((2, 3, 64, 128), 2)
@@ -1066,7 +1033,7 @@ def test_cfnet_state_dict_keys_match_reference():
 
 def _cfnet_filled(D):
     from stereo_toolbox_amd.models import CFNet
-    m, sd = _filled(CFNet, D)
+    m, sd = filled(CFNet, D)
     with torch.no_grad():                       # the range parameters start at 0 in the reference; exercise them
         m.gamma_s3.fill_(0.25); m.beta_s3.fill_(0.5); m.gamma_s2.fill_(0.15); m.beta_s2.fill_(0.3)
     for k, v in (("gamma_s3", 0.25), ("beta_s3", 0.5), ("gamma_s2", 0.15), ("beta_s2", 0.3)):

@@ -22,9 +22,8 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.mono_align_config import (ALIGN_ARGS, ALIGN_FIELDS, ALIGN_INPUTS, LRC_CASES, LRC_THRESHOLDS, LSQ_CASES, MASK_CASES,
                                             MIRROR_THRESHOLDS, QUANTILES, align_inputs, lrc_inputs, lsq_inputs, mask_inputs,
                                             mirror_inputs)
-from tests.test_geo_lookup import VALUE_FACTOR, env  # noqa: F401
-from tests.test_models import GRAD_FACTOR, Env
-from tests.test_stereoanywhere import _on, _pin, _sync, _within, truncation_mask
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, Env, env, on, pin_fixture, sync, within_fixture  # noqa: F401
+from tests.restated import truncation_mask
 from stereo_toolbox_amd.utils import synthetic_tensor
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mono_align.npz")
@@ -157,28 +156,28 @@ def test_fixture_tells_fp32_thresholds_from_double_thresholds(gold):
 def test_softlrc_restatement_matches_reference_fixture(gold, tag):
     r64, r32 = _restated_lrc(tag, torch.float64), _restated_lrc(tag, torch.float32)
     for k in r64:
-        _pin(gold, f"lrc:{tag}:{k}", r64[k], r32[k])
+        pin_fixture(r64[k], r32[k], gold, f"lrc:{tag}:{k}")
 
 
 @pytest.mark.parametrize("tag", list(LSQ_CASES))
 def test_weighted_lsq_restatement_matches_reference_fixture(gold, tag):
     r64, r32 = _restated_lsq(tag, torch.float64), _restated_lsq(tag, torch.float32)
     for k in r64:
-        _pin(gold, f"lsq:{tag}:{k}", r64[k], r32[k])
+        pin_fixture(r64[k], r32[k], gold, f"lsq:{tag}:{k}")
 
 
 @pytest.mark.parametrize("name", list(MIRROR_THRESHOLDS))
 def test_mirror_restatement_matches_reference_fixture(gold, name):
     r64, r32 = _restated_mirror(name, torch.float64), _restated_mirror(name, torch.float32)
     for k in r64:
-        _pin(gold, f"mirror:{name}:{k}", r64[k], r32[k])
+        pin_fixture(r64[k], r32[k], gold, f"mirror:{name}:{k}")
 
 
 def test_align_restatement_matches_reference_fixture(gold):
     r64, r32 = _restated_align(torch.float64), _restated_align(torch.float32)
     assert len(r64) == len(ALIGN_FIELDS) + len(ALIGN_INPUTS)
     for k in r64:
-        _pin(gold, f"align:{k}", r64[k], r32[k])
+        pin_fixture(r64[k], r32[k], gold, f"align:{k}")
 
 
 # ------------------------------------------------------------------------------------------ masks and the masked volume: exact
@@ -192,11 +191,11 @@ def _masked_volume(env, tag):
         out = SA.masked_volume(v, left, right, N)
         loss = (out * gw).sum()
         loss.backward(retain_graph=True)
-        _sync(env)
+        sync(env)
     return ml, mr, out, v, loss
 
 
-@pytest.mark.parametrize("backend,tag", _on(MASK_CASES))
+@pytest.mark.parametrize("backend,tag", on(MASK_CASES))
 def test_masks_and_masked_volume_equal_reference(backend, tag, gold):
     env_ = Env(backend)
     B, N, H, W2, W3 = MASK_CASES[tag]
@@ -218,7 +217,7 @@ def test_masked_volume_gives_zero_for_a_non_finite_entry_under_a_zero_mask(env):
     left[0, 0, 0, 0], right[0, 0, 0, :4] = 0.05, 0.95                    # bins 0 and 7: nothing of the row's start survives
     with env.ctx():
         out = SA.masked_volume(vol.to(env.device), left.to(env.device), right.to(env.device), 8)
-        _sync(env)
+        sync(env)
     assert (out[0, :, 0, 0, :4] == 0).all() and torch.isfinite(out).all()
 
 
@@ -231,11 +230,11 @@ def _softlrc(env, tag, which=(0, 1)):
         outs = SA.softlrc(a, b, lrc_th=LRC_THRESHOLDS[tag])
         loss = sum((outs[i] * gws[i].to(env.device)).sum() for i in which)
         loss.backward(retain_graph=True)
-        _sync(env)
+        sync(env)
     return outs, a, b, loss
 
 
-@pytest.mark.parametrize("backend,tag", _on(LRC_CASES))
+@pytest.mark.parametrize("backend,tag", on(LRC_CASES))
 def test_softlrc_matches_reference_fp64(backend, tag, gold, parity_log):
     env_ = Env(backend)
     B, H, W, _ = LRC_CASES[tag]
@@ -244,8 +243,7 @@ def test_softlrc_matches_reference_fp64(backend, tag, gold, parity_log):
                            ("g_disp3", b.grad, GRAD_FACTOR)):
         assert got.shape == (B, 1, H, W) and got.dtype == torch.float32
         key = f"lrc:{tag}:{k}"
-        _within(parity_log, got, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), factor,
-                f"mono_align softlrc {tag} {k} [{backend}]")
+        within_fixture(got, gold, key, factor, f"mono_align softlrc {tag} {k} [{backend}]", parity_log)
 
 
 def test_softlrc_gradient_of_one_output_alone(env, gold, parity_log):  # noqa: F811
@@ -255,8 +253,7 @@ def test_softlrc_gradient_of_one_output_alone(env, gold, parity_log):  # noqa: F
     _, a1, b1, _ = _softlrc(env, "px37", which=(1,))
     for k, got in (("g_disp2", a0.grad.double() + a1.grad.double()), ("g_disp3", b0.grad.double() + b1.grad.double())):
         key = f"lrc:px37:{k}"
-        _within(parity_log, got, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), GRAD_FACTOR,
-                f"mono_align softlrc px37 {k} summed [{env.name}]")
+        within_fixture(got, gold, key, GRAD_FACTOR, f"mono_align softlrc px37 {k} summed [{env.name}]", parity_log)
 
 
 # ------------------------------------------------------------------------------------------ weighted_lsq vs fp64
@@ -268,11 +265,11 @@ def _weighted_lsq(env, tag):
         scale, shift = SA.weighted_lsq(m, d, c, min_quantile=QUANTILES[0], max_quantile=QUANTILES[1])
         loss = (scale * gws[0].to(env.device)).sum() + (shift * gws[1].to(env.device)).sum()
         loss.backward(retain_graph=True)
-        _sync(env)
+        sync(env)
     return {"scale": scale, "shift": shift, "g_mde": m.grad, "g_disp": d.grad, "g_conf": c.grad}, (m, d, c), loss
 
 
-@pytest.mark.parametrize("backend,tag", _on(LSQ_CASES))
+@pytest.mark.parametrize("backend,tag", on(LSQ_CASES))
 def test_weighted_lsq_matches_reference_fp64(backend, tag, gold, parity_log):
     from stereo_toolbox_amd import ops
     env_ = Env(backend)
@@ -282,11 +279,11 @@ def test_weighted_lsq_matches_reference_fp64(backend, tag, gold, parity_log):
     for k, t in got.items():
         assert t.dtype == torch.float32
         key = f"lsq:{tag}:{k}"
-        _within(parity_log, t, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]),
-                GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR, f"mono_align weighted_lsq {tag} {k} [{backend}]")
+        within_fixture(t, gold, key, GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR,
+                       f"mono_align weighted_lsq {tag} {k} [{backend}]", parity_log)
     with env_.ctx():
         th = ops.quantile_thresholds(d.detach(), *QUANTILES)
-        _sync(env_)
+        sync(env_)
     assert torch.equal(th.cpu(), torch.from_numpy(gold[f"lsq:{tag}:thresholds:f32"]))    # torch.quantile, fp32, on the CPU
 
 
@@ -300,7 +297,7 @@ def test_quantile_thresholds_equal_torch_quantile_bit_for_bit(env):  # noqa: F81
         disp[2] = torch.round(disp[2])
         with env.ctx():
             got = ops.quantile_thresholds(disp, *qs)
-            _sync(env)
+            sync(env)
         want = torch.stack([torch.stack([torch.quantile(torch.relu(disp[b].flatten()), q) for q in qs]) for b in range(3)])
         assert got.dtype == torch.float32 and torch.equal(got, want), (n, got, want)
 
@@ -313,7 +310,7 @@ def test_weighted_lsq_singular_system_gives_the_weighted_mean(env):  # noqa: F81
     conf = torch.ones(1, 1, 2, 8)
     with env.ctx():
         scale, shift = SA.weighted_lsq(mde.to(env.device), disp.to(env.device), conf.to(env.device), 0.0, 1.0)
-        _sync(env)
+        sync(env)
     assert scale.item() == 0.0 and shift.item() == 7.5
 
 
@@ -326,18 +323,18 @@ def _mirror(env, name):
         out = SA.handcrafted_mirror_detector(*xs, conf_th=MIRROR_THRESHOLDS[name])
         loss = (out * gw.to(env.device)).sum()
         loss.backward(retain_graph=True)
-        _sync(env)
+        sync(env)
     return {"out": out, "g_sd": xs[0].grad, "g_md": xs[1].grad, "g_sc": xs[2].grad, "g_mc": xs[3].grad}, xs, loss
 
 
-@pytest.mark.parametrize("backend,name", _on(MIRROR_THRESHOLDS))
+@pytest.mark.parametrize("backend,name", on(MIRROR_THRESHOLDS))
 def test_mirror_detector_matches_reference_fp64(backend, name, gold, parity_log):
     got, _, _ = _mirror(Env(backend), name)
     for k, t in got.items():
         assert t.dtype == torch.float32
         key = f"mirror:{name}:{k}"
-        _within(parity_log, t, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]),
-                GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR, f"mono_align mirror {name} {k} [{backend}]")
+        within_fixture(t, gold, key, GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR,
+                       f"mono_align mirror {name} {k} [{backend}]", parity_log)
 
 
 def _align(env):
@@ -348,7 +345,7 @@ def _align(env):
         res = SA.align_mono(*(x[k] for k in ALIGN_INPUTS), **ALIGN_ARGS)
         loss = sum((getattr(res, f) * g.to(env.device)).sum() for f, g in gws.items())
         loss.backward(retain_graph=True)
-        _sync(env)
+        sync(env)
     return res, x, loss
 
 
@@ -357,12 +354,10 @@ def test_align_mono_matches_reference_fp64(env, gold, parity_log):  # noqa: F811
     assert res._fields == ALIGN_FIELDS and res.truncate_mask.requires_grad is False
     for f in ALIGN_FIELDS:
         key = f"align:{f}"
-        _within(parity_log, getattr(res, f), torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), VALUE_FACTOR,
-                f"mono_align align_mono {f} [{env.name}]")
+        within_fixture(getattr(res, f), gold, key, VALUE_FACTOR, f"mono_align align_mono {f} [{env.name}]", parity_log)
     for k in ALIGN_INPUTS:
         key = f"align:g_{k}"
-        _within(parity_log, x[k].grad, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), GRAD_FACTOR,
-                f"mono_align align_mono g_{k} [{env.name}]")
+        within_fixture(x[k].grad, gold, key, GRAD_FACTOR, f"mono_align align_mono g_{k} [{env.name}]", parity_log)
 
 
 def test_drop_in_one_liners(env):  # noqa: F811
@@ -407,7 +402,7 @@ def test_bitwise_reproducible_and_second_backward_equals_the_first(env, what):  
         t.grad = None
     with env.ctx():
         a_loss.backward()
-        _sync(env)
+        sync(env)
     assert all(torch.equal(p, q) for p, q in zip(first, _grads(a_leaves)))
 
 

@@ -8,7 +8,7 @@ csrc/selfsup_loss.hip, through `stereo_toolbox_amd.loss_functions`.
   fp64 to 1e-11 (whole tensors or the subsample), in fp32 to 2 x d_ref -- so the fixture and the restatement check each other.
 * The product (emulator build here, gfx950 with `-m gpu`) is compared with the fp64 fixture -- for the GPU-only case with the
   restatement evaluated in fp64 at test time: values within VALUE_FACTOR (2) x d_ref, gradients within GRAD_FACTOR (3) x d_ref,
-  floor 2e-7 * max(1, max|want|) where d_ref is zero (the rule of tests/test_geo_lookup._within).  Every element of every tensor
+  floor 2e-7 * max(1, max|want|) where d_ref is zero (the rule of tests/parity.within).  Every element of every tensor
   is compared and the achieved ratios go to the parity report.
 * auto_mask: the product's bool map against the fp64 one; a pixel may be skipped only where the fp64 errors are within 1e-5 of
   each other, at most 1 % of a case; both outcomes must hold at least 5 % of the fp64 map.
@@ -27,8 +27,7 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.selfsup_config import (AUTO_MASK_CASES, AUTO_MASK_DENORM, AUTO_MASK_MARGIN, AUTO_MASK_MAX_SKIPPED,
                                          AUTO_MASK_MIN_SHARE, CASES, FD_SHAPE, GPU_ONLY, PACKAGE_EXPORTS, REQUIRED, SSIM_WEIGHT,
                                          SSIM_WINDOW_CASES, SUBSAMPLE, SURFACE, fd_inputs, inputs, normalised, subsample)
-from tests.test_geo_lookup import VALUE_FACTOR, env  # noqa: F401
-from tests.test_models import GRAD_FACTOR, Env
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, Env, directional, env, on, pin_fixture, pin_subsample, sync, within  # noqa: F401
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "selfsup_loss.npz")
 PKG = "stereo_toolbox_amd.loss_functions"
@@ -40,31 +39,9 @@ def gold():
     return np.load(GOLD)
 
 
-def _on(tags, gpu_only=()):
-    return [("emu", t) for t in tags if t not in gpu_only] + [pytest.param("hip", t, marks=pytest.mark.gpu) for t in tags]
-
-
-def _within(log, got, want64, dref, factor, what):
-    """tests/test_geo_lookup._within with the fp64 tensor given: |got - want| <= factor * d_ref over the whole tensor (floor
-    2e-7 * max(1, max|want|) where d_ref is zero); the achieved ratio is printed and goes to the parity report."""
-    got, want = got.detach().cpu().double(), want64.detach().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    tol = factor * dref if dref > 0 else 2e-7 * max(1.0, want.abs().max().item())
-    ratio = err / dref if dref else float("nan")
-    print(f"{what}: err {err:.3e}  d_ref {dref:.3e}  ratio {ratio:.2f}")
-    log(what, err=err, d_ref=dref, ratio=ratio, allowed=factor)
-    assert err <= tol, (what, err, dref)
-
-
 def _mods():
     return (importlib.import_module(PKG + ".photometric_loss"), importlib.import_module(PKG + ".auto_mask"),
             importlib.import_module(PKG + ".smoothness_loss"))
-
-
-def _sync(env):
-    if env.name == "hip":
-        torch.cuda.synchronize()
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
@@ -168,19 +145,12 @@ def test_restatement_matches_reference_fixture(gold, tag):
     assert len(r64) >= 13
     for k in r64:
         key = f"{tag}:{k}"
-        dref = float(gold[key + ":dref"])
-        assert dref > 0, key
         if tag in GPU_ONLY:
-            want, peak = torch.from_numpy(gold[key + ":sub"]), float(gold[key + ":max"])
-            got = subsample(r64[k])
-            assert got.shape == want.shape and want.numel() >= min(r64[k].numel(), SUBSAMPLE), key
-            assert abs(r64[k].abs().max().item() - peak) <= 1e-11 * max(1.0, peak), key
-            assert (got - want).abs().max().item() <= 1e-11 * max(1.0, peak), key
+            assert float(gold[key + ":dref"]) > 0, key
+            pin_subsample(r64[k], torch.from_numpy(gold[key + ":sub"]), float(gold[key + ":max"]), subsample,
+                          min(r64[k].numel(), SUBSAMPLE), key)
         else:
-            want64, want32 = torch.from_numpy(gold[key + ":f64"]), torch.from_numpy(gold[key + ":f32"])
-            assert r64[k].shape == want64.shape and r32[k].dtype == want32.dtype == torch.float32, key
-            assert (r64[k] - want64).abs().max().item() <= 1e-11 * max(1.0, want64.abs().max().item()), key
-            assert (r32[k] - want32).abs().max().item() <= 2 * dref, (key, (r32[k] - want32).abs().max().item(), dref)
+            pin_fixture(r64[k], r32[k], gold, key)
 
 
 # ------------------------------------------------------------------------------------------ the product vs fp64
@@ -217,7 +187,7 @@ def _product(env, tag):
         assert loss.dim() == 0 and loss.dtype == torch.float32
         res["smooth"] = loss.detach()
         res["g_smooth"], = torch.autograd.grad(loss, sdisp)
-        _sync(env)
+        sync(env)
     return {k: v.detach().cpu() for k, v in res.items()}
 
 
@@ -225,7 +195,7 @@ def _factor(k):
     return GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR
 
 
-@pytest.mark.parametrize("backend,tag", _on(CASES, GPU_ONLY))
+@pytest.mark.parametrize("backend,tag", on(CASES, GPU_ONLY))
 def test_product_matches_reference_fp64(backend, tag, gold, parity_log):
     """warped, valid_mask, the ssim map (windows 7 / 3 / 11), photometric_loss with the mask on and off and without a disparity,
     the smoothness scalar; the gradients to disp of warp, photometric and smoothness and to x and y of ssim."""
@@ -234,7 +204,7 @@ def test_product_matches_reference_fp64(backend, tag, gold, parity_log):
     assert set(got) == set(names)
     for k in names:
         want = _restated64(tag)[k] if tag in GPU_ONLY else torch.from_numpy(gold[f"{tag}:{k}:f64"])
-        _within(parity_log, got[k], want, float(gold[f"{tag}:{k}:dref"]), _factor(k), f"selfsup {tag} {k} [{backend}]")
+        within(got[k], want, float(gold[f"{tag}:{k}:dref"]), _factor(k), f"selfsup {tag} {k} [{backend}]", parity_log)
 
 
 def _check_mask(log, got, want64, reproj64, ident64, what):
@@ -250,7 +220,7 @@ def _check_mask(log, got, want64, reproj64, ident64, what):
     assert skipped <= AUTO_MASK_MAX_SKIPPED and wrong == 0, (what, skipped, wrong)
 
 
-@pytest.mark.parametrize("backend,tag", _on(AUTO_MASK_CASES))
+@pytest.mark.parametrize("backend,tag", on(AUTO_MASK_CASES))
 def test_auto_mask_matches_reference_fp64(backend, tag, gold, parity_log):
     _, A, _ = _mods()
     env = Env(backend)
@@ -268,7 +238,7 @@ def test_auto_mask_matches_reference_fp64(backend, tag, gold, parity_log):
                         f"selfsup {tag} auto_mask denorm [{backend}]")
 
 
-@pytest.mark.parametrize("backend,tag", _on(("r37x70",)))
+@pytest.mark.parametrize("backend,tag", on(("r37x70",)))
 def test_every_kernel_is_bitwise_reproducible(backend, tag):
     a, b = _product(Env(backend), tag), _product(Env(backend), tag)
     for k in a:
@@ -277,29 +247,6 @@ def test_every_kernel_is_bitwise_reproducible(backend, tag):
 
 
 # ------------------------------------------------------------------------------------------ finite differences (emulator)
-def _directional(fn, inputs, eps=3e-3, tol=3e-2, seed=0):
-    """The method of tests/test_hygiene._directional: <grad_i, v_i> against the central difference for every input."""
-    g = torch.Generator().manual_seed(seed)
-
-    def flat(y):
-        return torch.cat([t.reshape(-1) for t in y]) if isinstance(y, (list, tuple)) else y.reshape(-1)
-
-    xs = [t.clone().requires_grad_() for t in inputs]
-    y = flat(fn(*xs))
-    gy = torch.randn(y.shape, generator=g)
-    (y * gy).sum().backward()
-    for i, x in enumerate(xs):
-        v = torch.randn(x.shape, generator=g)
-        v *= float(x.detach().abs().mean()) / (v.norm() / (x.numel() ** 0.5))     # step relative to the input's magnitude
-        with torch.no_grad():
-            args_p = [t.detach() + (eps * v if j == i else 0) for j, t in enumerate(inputs)]
-            args_m = [t.detach() - (eps * v if j == i else 0) for j, t in enumerate(inputs)]
-            fd = ((flat(fn(*args_p)).double() - flat(fn(*args_m)).double()) * gy.double()).sum().item() / (2 * eps)
-        an = (x.grad.double() * v.double()).sum().item()
-        scale = max(abs(an), abs(fd), 1e-3 * (x.grad.norm().item() * v.norm().item()))
-        assert abs(an - fd) <= tol * scale, f"input {i}: analytic {an:.6e} vs finite difference {fd:.6e}"
-
-
 def test_finite_difference_gradients():
     """Directional derivatives through the product host code on the emulator at (1, 3, 9, 13).  The disparity steps (1e-3 of the
     mean |disp|, a few thousandths of a pixel) stay inside the 0.05 px the inputs keep from the bilinear kinks."""
@@ -310,12 +257,12 @@ def test_finite_difference_gradients():
     with emu_product_path():
         # (enable_mask=False: the reference detaches valid_mask, so with the mask on the gradient is NOT the derivative of the
         #  forward; the masked gradient is compared with the reference's in test_product_matches_reference_fp64)
-        _directional(lambda d: P.photometric_loss(left, right, d, enable_mask=False), [disp], eps=1e-3, seed=21)
-        _directional(lambda d: P.photometric_loss(left, right, d, ssim_weight=0.4, enable_mask=False), [disp], eps=1e-3, seed=22)
-        _directional(lambda d: P.warp_right_to_left(right, d)[0], [disp], eps=1e-3, seed=23)
-        _directional(lambda x, y: P.ssim(x, y), [left, right], seed=24)
-        _directional(lambda x, y: P.ssim(x, y, window_size=3), [left, right], seed=25)
-        _directional(lambda d: S.smoothness_loss(d, left, warn=False).reshape(1), [disp.abs() + 1], eps=1e-3, seed=26)
+        directional(lambda d: P.photometric_loss(left, right, d, enable_mask=False), [disp], eps=1e-3, seed=21)
+        directional(lambda d: P.photometric_loss(left, right, d, ssim_weight=0.4, enable_mask=False), [disp], eps=1e-3, seed=22)
+        directional(lambda d: P.warp_right_to_left(right, d)[0], [disp], eps=1e-3, seed=23)
+        directional(lambda x, y: P.ssim(x, y), [left, right], seed=24)
+        directional(lambda x, y: P.ssim(x, y, window_size=3), [left, right], seed=25)
+        directional(lambda d: S.smoothness_loss(d, left, warn=False).reshape(1), [disp.abs() + 1], eps=1e-3, seed=26)
 
 
 # ------------------------------------------------------------------------------------------ warning, refusals, surface

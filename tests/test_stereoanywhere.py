@@ -5,11 +5,12 @@ of csrc/allpairs.hip: the four estimates regressed from the all-pairs volume, th
   tests/golden/stereoanywhere_config.py, in fp32 and in fp64, and per tensor d_ref = max|fp32 - fp64| > 0
   (tests/golden/make_golden_stereoanywhere.py).  The volume gradients of the larger estimator cases keep d_ref, max|fp64| and a
   strided subsample of the fp64 tensor.
-* A plain-torch restatement lives in this file and is pinned to the fixture on the CPU first -- in fp64 to 1e-11 (whole tensors or
-  the subsample), in fp32 to 2 x d_ref -- so the fixture and the restatement check each other.
+* A plain-torch restatement lives in this file (the truncation mask, shared with tests/test_mono_align.py, in tests/restated.py) and
+  is pinned to the fixture on the CPU first -- in fp64 to 1e-11 (whole tensors or the subsample), in fp32 to 2 x d_ref -- so the
+  fixture and the restatement check each other.
 * The product (emulator build here, gfx950 with `-m gpu`) is compared with the fp64 fixture -- for the subsampled tensors with the
   restatement evaluated in fp64 at test time: values within VALUE_FACTOR (2) x d_ref, gradients within GRAD_FACTOR (3) x d_ref,
-  floor 2e-7 * max(1, max|want|) where d_ref is zero (the rule of tests/test_geo_lookup._within).  Every element of every tensor is
+  floor 2e-7 * max(1, max|want|) where d_ref is zero (the rule of tests/parity.within).  Every element of every tensor is
   compared and the achieved ratios go to the parity report.
 """
 import functools
@@ -23,8 +24,8 @@ import torch
 from tests.backends import be, ptr  # noqa: F401
 from tests.golden.stereoanywhere_config import (ATTENUATION, BLOCK_CASES, EST_CASES, EST_GPU_ONLY, EST_WHOLE, MASK_THRESHOLDS, OUTPUTS,
                                                 SUBSAMPLE, block_inputs, block_out_width, est_inputs, mask_inputs, subsample)
-from tests.test_geo_lookup import EPS, VALUE_FACTOR, _near, _pack, env, pool, sample  # noqa: F401
-from tests.test_models import GRAD_FACTOR, Env
+from tests.parity import EPS, GRAD_FACTOR, VALUE_FACTOR, Env, env, near, on, pin_fixture, pin_subsample, sync, within, within_fixture  # noqa: F401
+from tests.restated import _pack, pool, sample, truncation_mask
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stereoanywhere.npz")
 
@@ -32,23 +33,6 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stere
 @pytest.fixture(scope="module")
 def gold():
     return np.load(GOLD)
-
-
-def _on(tags, gpu_only=()):
-    return [("emu", t) for t in tags if t not in gpu_only] + [pytest.param("hip", t, marks=pytest.mark.gpu) for t in tags]
-
-
-def _within(log, got, want64, dref, factor, what):
-    """tests/test_geo_lookup._within with the fp64 tensor given: |got - want| <= factor * d_ref over the whole tensor (floor
-    2e-7 * max(1, max|want|) where d_ref is zero); the achieved ratio is printed and goes to the parity report."""
-    got, want = got.detach().cpu().double(), want64.detach().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    tol = factor * dref if dref > 0 else 2e-7 * max(1.0, want.abs().max().item())
-    ratio = err / dref if dref else float("nan")
-    print(f"{what}: err {err:.3e}  d_ref {dref:.3e}  ratio {ratio:.2f}")
-    log(what, err=err, d_ref=dref, ratio=ratio, allowed=factor)
-    assert err <= tol, (what, err, dref)
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
@@ -63,15 +47,6 @@ def estimates(volume):
     conf_l = 1 - (-torch.sum(pl * torch.log2(pl + 1e-6), dim=3) / math.log2(W2))
     conf_r = 1 - (-torch.sum(pr * torch.log2(pr + 1e-6), dim=2) / math.log2(W1))
     return tuple(t.unsqueeze(1) for t in (disp_l, conf_l, disp_r, conf_r))
-
-
-def truncation_mask(disp, conf, conf_th, atten):
-    """[B,1,H,W] x 2 -> [B,1,H,W,W], utils/utils.py:216-238"""
-    W = disp.shape[3]
-    a = torch.arange(W, dtype=disp.dtype)
-    c = (conf if conf_th is None else (conf > conf_th).to(disp.dtype)).unsqueeze(4)
-    x = (a.view(1, 1, 1, W) - disp).unsqueeze(4) - a.view(1, 1, 1, 1, W)
-    return 1 * (1 - c) + c * (torch.sigmoid(x) * (1 - atten) + atten)
 
 
 def block_pyramid(vol, maps, L):
@@ -122,19 +97,11 @@ def _restated_block(tag, dtype):
 
 
 def _pin(gold, key, r64, r32):
-    dref = float(gold[key + ":dref"])
-    assert dref > 0, key
     if key + ":f64" in gold:
-        want64, want32 = torch.from_numpy(gold[key + ":f64"]), torch.from_numpy(gold[key + ":f32"])
-        assert r64.shape == want64.shape and r32.dtype == want32.dtype == torch.float32, key
-        assert (r64 - want64).abs().max().item() <= 1e-11 * max(1.0, want64.abs().max().item()), key
-        assert (r32 - want32).abs().max().item() <= 2 * dref, key
+        pin_fixture(r64, r32, gold, key)
     else:
-        want, peak = torch.from_numpy(gold[key + ":sub"]), float(gold[key + ":max"])
-        got = subsample(r64)
-        assert got.shape == want.shape and want.numel() >= min(r64.numel(), SUBSAMPLE), key
-        assert abs(r64.abs().max().item() - peak) <= 1e-11 * max(1.0, peak), key
-        assert (got - want).abs().max().item() <= 1e-11 * max(1.0, peak), key
+        assert float(gold[key + ":dref"]) > 0, key
+        pin_subsample(r64, torch.from_numpy(gold[key + ":sub"]), float(gold[key + ":max"]), subsample, min(r64.numel(), SUBSAMPLE), key)
 
 
 @pytest.mark.parametrize("tag", list(EST_CASES))
@@ -166,11 +133,6 @@ def _want(gold, tag, k):
     return want, float(gold[key + ":dref"])
 
 
-def _sync(env):
-    if env.name == "hip":
-        torch.cuda.synchronize()
-
-
 def _estimates_together(env, tag, only=None):
     """estimate_all, the loss on all four outputs or on output `only` alone -> (outputs, volume gradient)"""
     from stereo_toolbox_amd.models import StereoAnywhere as SA
@@ -179,7 +141,7 @@ def _estimates_together(env, tag, only=None):
     with env.ctx():
         outs = SA.estimate_all(v)
         sum((o * g.to(env.device)).sum() for i, (o, g) in enumerate(zip(outs, gws)) if only is None or only == i).backward()
-        _sync(env)
+        sync(env)
     return outs, v.grad
 
 
@@ -191,11 +153,11 @@ def _estimate_alone(env, tag, i):
     with env.ctx():
         out = fn(v)
         (out * gws[i].to(env.device)).sum().backward()
-        _sync(env)
+        sync(env)
     return out, v.grad
 
 
-@pytest.mark.parametrize("backend,tag", _on(EST_CASES, EST_GPU_ONLY))
+@pytest.mark.parametrize("backend,tag", on(EST_CASES, EST_GPU_ONLY))
 def test_estimates_match_reference_fp64(backend, tag, gold, parity_log):
     """All four outputs from one call and each asked for alone (bitwise the same), the volume gradient of the summed loss and of
     each output's loss alone -- fed alone to the four-output node and through the single-output call (bitwise the same)."""
@@ -204,15 +166,15 @@ def test_estimates_match_reference_fp64(backend, tag, gold, parity_log):
     outs, g_all = _estimates_together(env, tag)
     for i, k in enumerate(OUTPUTS):
         assert outs[i].shape == (B, 1, H, W2 if i >= 2 else W1) and outs[i].dtype == torch.float32
-        _within(parity_log, outs[i], *_want(gold, tag, k), VALUE_FACTOR, f"stereoanywhere {tag} {k} [{backend}]")
+        within(outs[i], *_want(gold, tag, k), VALUE_FACTOR, f"stereoanywhere {tag} {k} [{backend}]", parity_log)
     assert g_all.shape == (B, 1, H, W1, W2)
-    _within(parity_log, g_all, *_want(gold, tag, "g_all"), GRAD_FACTOR, f"stereoanywhere {tag} g_all [{backend}]")
+    within(g_all, *_want(gold, tag, "g_all"), GRAD_FACTOR, f"stereoanywhere {tag} g_all [{backend}]", parity_log)
     for i, k in enumerate(OUTPUTS):
         alone, g_alone = _estimate_alone(env, tag, i)
         assert torch.equal(alone, outs[i]), k
         _, g_fed = _estimates_together(env, tag, only=i)
         assert torch.equal(g_fed, g_alone), k
-        _within(parity_log, g_alone, *_want(gold, tag, "g_" + k), GRAD_FACTOR, f"stereoanywhere {tag} g_{k} [{backend}]")
+        within(g_alone, *_want(gold, tag, "g_" + k), GRAD_FACTOR, f"stereoanywhere {tag} g_{k} [{backend}]", parity_log)
 
 
 def test_vol_pad_crops_the_disparities(env):
@@ -252,7 +214,7 @@ def _block_case(env, tag, fused=True, cls=None, retain=False):
         outs = [fn(c.to(dev)) for c in coords]
         loss = sum((o * g.to(dev)).sum() for o, g in zip(outs, gws)) + (fn.corr_pyramid * _pack(wc).to(dev)).sum()
         loss.backward(retain_graph=retain)
-        _sync(env)
+        sync(env)
     return outs, v, loss
 
 
@@ -261,9 +223,7 @@ def _check_block(env, gold, log, tag, outs, grad, how=""):
     for o in outs:
         assert o.shape == (B, L * (2 * r + 1), H, block_out_width(tag)) and o.dtype == torch.float32 and o.is_contiguous()
     for k, got, factor in (("outs", torch.stack(outs), VALUE_FACTOR), ("g_fullcorr", grad, GRAD_FACTOR)):
-        key = f"block:{tag}:{k}"
-        _within(log, got, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), factor,
-                f"stereoanywhere block {tag}{how} {k} [{env.name}]")
+        within_fixture(got, gold, f"block:{tag}:{k}", factor, f"stereoanywhere block {tag}{how} {k} [{env.name}]", log)
 
 
 @pytest.mark.parametrize("tag", list(BLOCK_CASES))
@@ -289,7 +249,7 @@ def test_fast_block_is_the_same_object_and_static_corr(env):
         corr = SA.CorrBlock1D.corr(n2.to(env.device), n3.to(env.device))
     assert corr.shape == (2, 4, 19, 1, 23) and corr.dtype == torch.float32
     want = torch.einsum("aijk,aijh->ajkh", n2.double(), n3.double()).unsqueeze(3) / math.sqrt(3.0)
-    _near(corr, want, 3 * EPS, "static corr")
+    near(corr, want, 3 * EPS, "static corr")
 
 
 def test_block_is_bitwise_reproducible_and_second_backward_equals_the_first(env):
@@ -300,7 +260,7 @@ def test_block_is_bitwise_reproducible_and_second_backward_equals_the_first(env)
     first, a_v.grad = a_v.grad.clone(), None
     with env.ctx():
         loss.backward()
-        _sync(env)
+        sync(env)
     assert torch.equal(first, a_v.grad)
 
 
@@ -313,8 +273,7 @@ def test_truncation_mask_matches_reference_fp64(env, gold, parity_log, name):
                                           attenuation_gain=ATTENUATION)
     key = f"mask:{name}"
     assert mask.shape == tuple(gold[key + ":f64"].shape) and mask.dtype == torch.float32
-    _within(parity_log, mask, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), VALUE_FACTOR,
-            f"stereoanywhere {name} [{env.name}]")
+    within_fixture(mask, gold, key, VALUE_FACTOR, f"stereoanywhere {name} [{env.name}]", parity_log)
 
 
 # ------------------------------------------------------------------------------------------ refusals

@@ -29,9 +29,7 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.sttr_attention_config import (CORE, CORE_GPU_ONLY, TRANSFORMER, TRANSFORMER_GPU_ONLY, core_inputs, core_layout,
                                                 fill_parameters, is_whole, parameter_seed, sine_table, subsample, transformer_inputs,
                                                 transformer_layout, transformer_parameters)
-from tests.test_geo_lookup import VALUE_FACTOR, env  # noqa: F401
-from tests.test_models import GRAD_FACTOR, Env
-from tests.test_stereoanywhere import _on, _sync, _within
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, Env, env, on, sync, within  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "sttr_attention.npz")
@@ -217,11 +215,11 @@ def _want(gold, key, k):
     return (want64 if want64 is not None else _restated64(key)[k]), dref
 
 
-def _within_inf(log, got, want64, dref, factor, what):
-    """_within over the finite entries; the -inf entries compared by equality"""
+def _within_inf(got, want64, dref, factor, what, log):
+    """tests/parity.within over the finite entries; the -inf entries compared by equality"""
     inf = torch.isinf(want64)
     assert torch.equal(got.detach().cpu() == NINF, inf), what
-    _within(log, got.detach().cpu().masked_fill(inf, 0.0), want64.masked_fill(inf, 0.0), dref, factor, what)
+    within(got.detach().cpu().masked_fill(inf, 0.0), want64.masked_fill(inf, 0.0), dref, factor, what, log)
 
 
 # ------------------------------------------------------------------------------------------ the product vs fp64
@@ -250,7 +248,7 @@ def _core(env, tag, via):
             v_o = F.linear(o.view(W, B, C), mha.out_proj.weight, mha.out_proj.bias)
         assert not attn.requires_grad
         ((v_o * x["g_vo"].to(dev)).sum() + (raw.masked_fill(raw == NINF, 0.0) * x["g_raw"].to(dev)).sum()).backward()
-        _sync(env)
+        sync(env)
     res = {"v_o": v_o, "raw_attn": raw, "attn": attn, "g_query": query.grad}
     if kind == "cross":
         res["g_key"] = key.grad
@@ -259,7 +257,7 @@ def _core(env, tag, via):
 
 
 @pytest.mark.parametrize("via", ["module", "op"])
-@pytest.mark.parametrize("backend,tag", _on(list(CORE), CORE_GPU_ONLY))
+@pytest.mark.parametrize("backend,tag", on(list(CORE), CORE_GPU_ONLY))
 def test_attention_matches_reference_fp64(backend, tag, via, gold, parity_log):
     """v_o, raw_attn (-inf pattern by equality), attn (the op's `avg`) and every gradient of one attention call."""
     env = Env(backend)
@@ -268,8 +266,8 @@ def test_attention_matches_reference_fp64(backend, tag, via, gold, parity_log):
     assert set(got) == {k for k, _ in core_layout(tag)}
     for k, shape in core_layout(tag):
         assert tuple(got[k].shape) == shape and got[k].dtype == torch.float32, k
-        _within_inf(parity_log, got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR,
-                    f"sttr attention {tag} {k} {via} [{backend}]")
+        _within_inf(got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR,
+                    f"sttr attention {tag} {k} {via} [{backend}]", parity_log)
 
 
 def _model(tag, device):
@@ -277,7 +275,7 @@ def _model(tag, device):
     return fill_parameters(STTR.Transformer(C, E, L), parameter_seed(tag)).to(device)
 
 
-@pytest.mark.parametrize("backend,tag", _on([t for t in TRANSFORMER if t != "t17b"], TRANSFORMER_GPU_ONLY))
+@pytest.mark.parametrize("backend,tag", on([t for t in TRANSFORMER if t != "t17b"], TRANSFORMER_GPU_ONLY))
 def test_transformer_matches_reference_fp64(backend, tag, gold, parity_log):
     """attn_weight, both feature gradients and every parameter gradient; `norm.*` receive none."""
     env = Env(backend)
@@ -287,7 +285,7 @@ def test_transformer_matches_reference_fp64(backend, tag, gold, parity_log):
     with env.ctx():
         attn = model(left, right, x["pos"])
         (attn.masked_fill(attn == NINF, 0.0) * x["g_attn"]).sum().backward()
-        _sync(env)
+        sync(env)
     key = "transformer:" + tag
     got = {"attn_weight": attn, "g_feat_left": left.grad, "g_feat_right": right.grad}
     got.update({"g:" + n: p.grad for n, p in model.named_parameters()})
@@ -295,8 +293,8 @@ def test_transformer_matches_reference_fp64(backend, tag, gold, parity_log):
     assert set(got) == {k for k, _ in transformer_layout(tag)}
     for k, shape in transformer_layout(tag):
         assert tuple(got[k].shape) == shape, k
-        _within_inf(parity_log, got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g") else VALUE_FACTOR,
-                    f"sttr transformer {tag} {k} [{backend}]")
+        _within_inf(got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g") else VALUE_FACTOR,
+                    f"sttr transformer {tag} {k} [{backend}]", parity_log)
 
 
 def test_batch_of_two_gives_each_samples_record(env, gold, parity_log):  # noqa: F811
@@ -310,10 +308,10 @@ def test_batch_of_two_gives_each_samples_record(env, gold, parity_log):  # noqa:
     with env.ctx():
         attn = model(left, right, xs[0]["pos"].to(env.device))
         (attn.masked_fill(attn == NINF, 0.0) * cat["g_attn"]).sum().backward()
-        _sync(env)
+        sync(env)
     for n, tag in enumerate(tags):
         for k, t, f in (("attn_weight", attn, VALUE_FACTOR), ("g_feat_left", left.grad, GRAD_FACTOR), ("g_feat_right", right.grad, GRAD_FACTOR)):
-            _within_inf(parity_log, t[n:n + 1], *_want(gold, "transformer:" + tag, k), f, f"sttr transformer N=2 sample {n} {k} [{env.name}]")
+            _within_inf(t[n:n + 1], *_want(gold, "transformer:" + tag, k), f, f"sttr transformer N=2 sample {n} {k} [{env.name}]", parity_log)
 
 
 # ------------------------------------------------------------------------------------------ the op alone
@@ -332,7 +330,7 @@ def _op_run(env, xs, g_o, g_raw, causal, need_raw=True):
         if need_raw:
             loss = loss + (raw.masked_fill(raw == NINF, 0.0) * g_raw.to(env.device)).sum()
         loss.backward()
-        _sync(env)
+        sync(env)
     return [o, raw] + [None if t is None else t.grad for t in leaves]
 
 
@@ -362,7 +360,7 @@ def test_finite_difference_gradients(causal):
             assert abs(an - fd) <= 3e-2 * max(abs(an), abs(fd), 1e-3), (name, an, fd)
 
 
-@pytest.mark.parametrize("backend,tag", _on(["w17_cross", "w320_causal"], ["w320_causal"]))
+@pytest.mark.parametrize("backend,tag", on(["w17_cross", "w320_causal"], ["w320_causal"]))
 def test_outputs_are_bitwise_reproducible(backend, tag):
     """Forward and backward twice on fresh outputs: o, raw, dq, dk, dv and the table gradients dQr, dKr bit for bit."""
     env = Env(backend)
@@ -392,7 +390,7 @@ def test_causal_rows(env):  # noqa: F811
     with env.ctx():
         o2, raw2, _ = ops.sttr_rel_attention(*leaves, True, True, False)
         torch.autograd.backward([o2, raw2], [g_o.to(env.device), dirty.to(env.device)])
-        _sync(env)
+        sync(env)
     assert all(torch.equal(t.grad, c) for t, c in zip(leaves, clean[2:]))
 
 
@@ -506,7 +504,7 @@ def test_transformer_feeds_the_regression_head(env):  # noqa: F811
         attn = model(x["feat_left"], x["feat_right"], x["pos"])
         out = head(attn, STTR.NestedTensor(torch.zeros(1, 3, H, W, device=env.device), torch.zeros(1, 3, H, W, device=env.device)))
         (out["disp_pred"].sum() + out["occ_pred"].sum()).backward()
-        _sync(env)
+        sync(env)
     assert out["disp_pred"].shape == (1, H, W) and torch.isfinite(out["disp_pred"]).all() and torch.isfinite(out["occ_pred"]).all()
     g = model.self_attn_layers[0].self_attn.in_proj_weight.grad
     assert g is not None and torch.isfinite(g).all() and g.abs().max().item() > 0

@@ -26,11 +26,9 @@ import torch
 from stereo_toolbox_amd import ops
 from stereo_toolbox_amd.models import STTR
 from tests.backends import be, ptr  # noqa: F401
-from tests.golden.sttr_config import (CASE_VARIANTS, CASES, FORWARD_CASES, FORWARD_KEYS, GPU_ONLY, OUTPUTS, SCALE, VARIANTS, StandInCal,
-                                      forward_inputs, inputs, is_whole, layout, losses, outputs_of, subsample)
-from tests.test_geo_lookup import VALUE_FACTOR, env  # noqa: F401
-from tests.test_models import GRAD_FACTOR, Env
-from tests.test_stereoanywhere import _on, _sync, _within
+from tests.golden.sttr_config import (CASE_VARIANTS, CASES, FORWARD_CASES, FORWARD_KEYS, GPU_ONLY, OUTPUTS, SCALE, SUBSAMPLE, VARIANTS,
+                                      StandInCal, forward_inputs, inputs, is_whole, layout, losses, outputs_of, subsample)
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, Env, env, on, pin, pin_subsample, sync, within, within_fixture  # noqa: F401
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sttr_head.npz")
 RECORDS = [(tag, var) for tag in CASES for var in CASE_VARIANTS[tag]]
@@ -155,17 +153,12 @@ def test_restatement_matches_reference_fixture(gold, tag, var):
     rec = _record(gold, tag, var)
     assert set(rec) == set(r64)
     for k, (want64, want32, sub, dref, peak) in rec.items():
-        assert dref > 0 or (not VARIANTS[var][0] and k.endswith("bin_r")), k     # (softmax: the dustbin row is the constant 1 / M)
-        tol = 1e-11 * max(1.0, peak)
-        assert abs(r64[k].abs().max().item() - peak) <= tol, k
+        exact = not VARIANTS[var][0] and k.endswith("bin_r")     # (softmax: the dustbin row is the constant 1 / M, d_ref may be 0)
         if want64 is not None:
-            assert r32[k].dtype == torch.float32 and r64[k].shape == want64.shape, k
-            assert (r64[k] - want64).abs().max().item() <= tol, k
-            assert (r32[k] - want32).abs().max().item() <= 2 * dref, k
+            pin(r64[k], r32[k], want64, want32, dref, k, peak=peak, zero_dref="exact" if exact else None)
         else:
-            got = subsample(r64[k])
-            assert got.shape == sub.shape, k
-            assert (got - sub).abs().max().item() <= tol, k
+            assert dref > 0 or exact, k
+            pin_subsample(r64[k], sub, peak, subsample, SUBSAMPLE, k)
             assert (r32[k].double() - r64[k]).abs().max().item() <= 2 * dref, k
 
 
@@ -186,7 +179,7 @@ def _fused(env, tag, var, which="all"):
                                                             None if disp_gt is None else target_of(disp_gt).to(dev))
         out = {"disp": disp, "occ": occ, "gt": gt, "bin_l": bin_l, "bin_r": bin_r}
         sum((out[k] * gws[k].to(dev)).sum() for k in outputs_of(var) if which in ("all", k)).backward()
-        _sync(env)
+        sync(env)
     return out, arg, a.grad, p.grad
 
 
@@ -198,11 +191,11 @@ def _dense(env, tag, var, G=None):
         P = ops.sttr_optimal_transport(a, p, CASES[tag][3]) if ot else ops.sttr_softmax(a, p)
         if G is not None:
             (P * G.to(env.device)).sum().backward()
-        _sync(env)
+        sync(env)
     return P, a.grad, p.grad
 
 
-@pytest.mark.parametrize("backend,rec", _on(RECORDS, [r for r in RECORDS if r[0] in GPU_ONLY]))
+@pytest.mark.parametrize("backend,rec", on(RECORDS, [r for r in RECORDS if r[0] in GPU_ONLY]))
 def test_fused_head_matches_reference_fp64(backend, rec, gold, parity_log):
     """Every output, g_attn and g_phi of the summed loss and of each output's loss alone."""
     tag, var = rec
@@ -217,17 +210,17 @@ def test_fused_head_matches_reference_fp64(backend, rec, gold, parity_log):
             assert out["gt"] is None or "gt" in outs
             for k in outs:
                 assert out[k].shape == (N, H, W) and out[k].dtype == torch.float32
-                _within(parity_log, out[k], *_want(gold, tag, var, k), VALUE_FACTOR, f"{name} {k} [{backend}]")
+                within(out[k], *_want(gold, tag, var, k), VALUE_FACTOR, f"{name} {k} [{backend}]", parity_log)
             want_arg = regress(_restated64(tag, var)["P"], None, None)[1]
             assert arg.dtype == torch.int32 and torch.equal(arg.cpu().long() & 0xFFFF, want_arg)
         assert g_attn.shape == (N, H, W, W) and g_phi.shape == ()
         assert (g_attn.cpu()[torch.isinf(inputs(tag)["attn"])] == 0).all()
-        _within(parity_log, g_attn, *_want(gold, tag, var, "g_attn:" + which), GRAD_FACTOR, f"{name} g_attn:{which} [{backend}]")
+        within(g_attn, *_want(gold, tag, var, "g_attn:" + which), GRAD_FACTOR, f"{name} g_attn:{which} [{backend}]", parity_log)
         g_phis.append(g_phi)
-    _within(parity_log, torch.stack(g_phis), *_want(gold, tag, var, "g_phi"), GRAD_FACTOR, f"{name} g_phi [{backend}]")
+    within(torch.stack(g_phis), *_want(gold, tag, var, "g_phi"), GRAD_FACTOR, f"{name} g_phi [{backend}]", parity_log)
 
 
-@pytest.mark.parametrize("backend,rec", _on(RECORDS, [r for r in RECORDS if r[0] in GPU_ONLY]))
+@pytest.mark.parametrize("backend,rec", on(RECORDS, [r for r in RECORDS if r[0] in GPU_ONLY]))
 def test_dense_pair_matches_reference_fp64(backend, rec, gold, parity_log):
     """The dense matrix, and -- fed the fp64 gradient of the regression's summed loss with respect to P -- the same g_attn and
     g_phi as the fused head's."""
@@ -239,13 +232,13 @@ def test_dense_pair_matches_reference_fp64(backend, rec, gold, parity_log):
     sum((out[k] * gws[k].double()).sum() for k in outputs_of(var)).backward()
     P, g_attn, g_phi = _dense(env, tag, var, P64.grad.float())
     name = f"sttr dense {tag} {var}"
-    _within(parity_log, P, *_want(gold, tag, var, "P"), VALUE_FACTOR, f"{name} P [{backend}]")
-    _within(parity_log, g_attn, *_want(gold, tag, var, "g_attn:all"), GRAD_FACTOR, f"{name} g_attn [{backend}]")
+    within(P, *_want(gold, tag, var, "P"), VALUE_FACTOR, f"{name} P [{backend}]", parity_log)
+    within(g_attn, *_want(gold, tag, var, "g_attn:all"), GRAD_FACTOR, f"{name} g_attn [{backend}]", parity_log)
     want_phi, dref_phi = _want(gold, tag, var, "g_phi")
-    _within(parity_log, g_phi, want_phi[0], dref_phi, GRAD_FACTOR, f"{name} g_phi [{backend}]")
+    within(g_phi, want_phi[0], dref_phi, GRAD_FACTOR, f"{name} g_phi [{backend}]", parity_log)
 
 
-@pytest.mark.parametrize("backend,tag", _on(["w17", "w320"], ["w320"]))
+@pytest.mark.parametrize("backend,tag", on(["w17", "w320"], ["w320"]))
 def test_outputs_are_bitwise_reproducible(backend, tag):
     """Every output of the four kernels, twice (tests/test_hygiene._twice in spirit: fresh outputs, bit for bit)."""
     env = Env(backend)
@@ -324,15 +317,14 @@ def test_forward_matches_reference_fp64(env, gold, parity_log, name):  # noqa: F
     head, attn, x = _head(name, env.device)
     with env.ctx(), torch.no_grad():
         out = head(attn, x)
-        _sync(env)
+        sync(env)
     assert set(out) == set(FORWARD_KEYS if down else FORWARD_KEYS[:5])
     for k in out:
         key = f"fwd:{name}:{k}"
         if key + ":f64" not in gold:
             assert out[k] is None and (k == "gt_response" and not gt or k.startswith("gt_response_occ") and not mask), k
             continue
-        _within(parity_log, out[k], torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), VALUE_FACTOR,
-                f"sttr forward {name} {k} [{env.name}]")
+        within_fixture(out[k], gold, key, VALUE_FACTOR, f"sttr forward {name} {k} [{env.name}]", parity_log)
 
 
 def test_dense_methods_give_the_fused_outputs(env, gold, parity_log):  # noqa: F811
@@ -352,10 +344,10 @@ def test_dense_methods_give_the_fused_outputs(env, gold, parity_log):  # noqa: F
         gt, _ = head._compute_gt_location(float(SCALE), x["sampled_cols"].to(env.device), x["sampled_rows"].to(env.device),
                                           P[..., :-1, :-1], x["disp_gt"].to(env.device))
         assert torch.equal(head._softmax(attn.to(env.device)).sum(-1).cpu().round(decimals=4), torch.ones(1, 3, 18))
-        _sync(env)
-    _within(parity_log, disp, *_want(gold, tag, var, "disp"), VALUE_FACTOR, f"sttr steps disp [{env.name}]")
-    _within(parity_log, occ, *_want(gold, tag, var, "occ"), VALUE_FACTOR, f"sttr steps occ [{env.name}]")
-    _within(parity_log, gt, *_want(gold, tag, "ot", "gt"), VALUE_FACTOR, f"sttr steps gt [{env.name}]")
+        sync(env)
+    within(disp, *_want(gold, tag, var, "disp"), VALUE_FACTOR, f"sttr steps disp [{env.name}]", parity_log)
+    within(occ, *_want(gold, tag, var, "occ"), VALUE_FACTOR, f"sttr steps occ [{env.name}]", parity_log)
+    within(gt, *_want(gold, tag, "ot", "gt"), VALUE_FACTOR, f"sttr steps gt [{env.name}]", parity_log)
     S = torch.cat([torch.cat([attn, phi.expand(1, 3, 17, 1)], -1), phi.expand(1, 3, 1, 18)], -2)
     lm, l2w = constants(17)
     assert (((head._sinkhorn(S.double(), lm.expand(1, 3, 18), lm.expand(1, 3, 18), CASES[tag][3]) + l2w).exp() - _restated64(tag, var)["P"]).abs().max().item()) < 1e-12
@@ -378,7 +370,7 @@ def test_fully_masked_upper_triangle_is_finite(env):  # noqa: F811
             outs = ops.sttr_regress(a, p, ot, 10, None, target.to(env.device))
             sum(o.sum() for o in outs[:5]).backward()
             P = ops.sttr_optimal_transport(a, p, 10) if ot else ops.sttr_softmax(a, p)
-            _sync(env)
+            sync(env)
         assert all(torch.isfinite(o).all() for o in outs[:5]) and torch.isfinite(P).all()
         assert (P.cpu()[..., :W, :W][torch.isinf(attn)] == 0).all()
         g = a.grad.cpu()
