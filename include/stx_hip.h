@@ -139,6 +139,33 @@ int stx_conv3d_wgrad_bn(const float* x, const float* gy, const float* z, const f
                         const float* invstd, const float* gamma, const float* sums, float inv_n, int act, float* dz, float* dw,
                         float* workspace, int B, int D, int H, int W, int CF, int CC, void* stream);
 
+/* ---- Axial-planar Conv3d (csrc/conv3d_axial.hip) ----------------------------------------------------
+ * The two convolutions of FoundationStereo's Conv3dNormActReduced (reference FoundationStereo/submodule.py:89-114): stride 1,
+ * "same" zero padding, dense channels-last fp32 [B][D][H][W][C], exact fp32 MFMA (v_mfma_f32_16x16x4_f32).  Kernel shapes
+ * (kd,kh,kw): planar (1,3,3) and axial (kd,1,1) with kd odd, 3 <= kd <= 17.  Cin a multiple of 4 up to 192, Cout up to 192
+ * (stx_conv3d_axial_supported); wider outputs than one workgroup serves are sliced inside the launcher.
+ * Weights are packed on the device from the torch layout w[A][B][T], T = kd*kh*kw (stx_conv3d_axial_packed_floats(K, N, ...)
+ * floats for GEMM-K = K input and N output channels):
+ *   mode 0: forward (w = [Cout][Cin][T], K = Cin);  mode 1: data gradient (flipped taps, transposed channels: K = Cout, N = Cin).
+ * stx_conv3d_axial_fwd: out = act(conv(x) * scale[c] + bias[c] + residual), epilogue contract of stx_conv3d_fwd (activation
+ * code 0..3; scale / bias / residual / stats may be NULL); stats[rows][2][Cout] with rows = stx_conv3d_axial_fwd_stat_rows(same
+ * shape arguments): every row is written, nothing beyond is touched.  The data gradient is the same call on mode-1 weights with
+ * Cin and Cout exchanged.
+ * stx_conv3d_axial_wgrad: dw[CC][CF][T] = sum_vox x[vox + t - pad][cf] * gz[vox][cc] (x: layer input, gz: gradient of the raw
+ * output; CF and CC multiples of 4); partial sums in `workspace` (stx_conv3d_axial_wgrad_workspace_floats floats), reduced in a
+ * fixed order: bitwise reproducible, no atomics.  Unsupported shapes return an error (the *_floats / *_stat_rows queries 0)
+ * and launch nothing. */
+int stx_conv3d_axial_supported(int Cin, int Cout, int kd, int kh, int kw);
+long long stx_conv3d_axial_packed_floats(int K, int N, int kd, int kh, int kw);
+int stx_conv3d_axial_pack_weight(const float* w, float* wp, int A, int B, int kd, int kh, int kw, int mode, void* stream);
+long long stx_conv3d_axial_fwd_stat_rows(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
+int stx_conv3d_axial_fwd(const float* x, const float* wp, float* out, const float* scale, const float* bias,
+                         const float* residual, float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
+                         int kw, int act, void* stream);
+long long stx_conv3d_axial_wgrad_workspace_floats(int B, int D, int H, int W, int CF, int CC, int kd, int kh, int kw);
+int stx_conv3d_axial_wgrad(const float* x, const float* gz, float* dw, float* workspace, int B, int D, int H, int W, int CF,
+                           int CC, int kd, int kh, int kw, void* stream);
+
 /* 3x3 stride-1 Conv2d (padding 1, no bias), channels-last, of the 2-D feature CNN's BasicBlocks with 32 / 64 channels: forward
  * and data gradient (reference models/GwcNet/gwcnet.py:12-42 `convbn(in, out, 3, 1, pad, 1)` -> nn.Conv2d at 1/2 and 1/4
  * resolution; PSMNet/submodule.py:57-97; ACVNet/acv.py:15-40).  x [B][H][W][Cin], out [B][H][W][Cout], fp32.

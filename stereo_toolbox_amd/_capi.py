@@ -56,6 +56,14 @@ SIGNATURES = {
     "stx_conv3d_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "stx_conv3d_wgrad_bn_supported": [_I, _I, _I, _I, _I, _I],
     "stx_conv3d_wgrad_bn": [_P] * 9 + [_F, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    # conv3d_axial.hip
+    "stx_conv3d_axial_supported": [_I, _I, _I, _I, _I],
+    "stx_conv3d_axial_packed_floats": [_I, _I, _I, _I, _I],
+    "stx_conv3d_axial_pack_weight": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "stx_conv3d_axial_fwd_stat_rows": [_I] * 9,
+    "stx_conv3d_axial_fwd": [_P] * 7 + [_I] * 10 + [_P],
+    "stx_conv3d_axial_wgrad_workspace_floats": [_I] * 9,
+    "stx_conv3d_axial_wgrad": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     # conv2d.hip
     "stx_conv2d_supported": [_I, _I],
     "stx_conv2d_stat_rows": [_I],

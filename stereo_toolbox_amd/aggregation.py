@@ -254,6 +254,65 @@ def conv_block(x, conv, bn=None, relu=False, second=None, residual=None, mish=Fa
     return ops.BnActFn.apply(z1, bn.weight, bn.bias, None, None, None, residual, relu, st1, None, 1, defer)
 
 
+def _axial_cfg(conv):
+    """(kd, kh, kw) of an nn.Conv3d the axial-planar kernels serve (csrc/conv3d_axial.hip): stride 1, "same" zero padding,
+    dense, kernel (1,3,3) or (kd,1,1) with kd odd up to 17.  A bias is allowed (axial_conv_block folds it)."""
+    if not isinstance(conv, nn.Conv3d) or _is_transposed(conv):
+        raise ops.StxError("axial_conv_block: expected an nn.Conv3d")
+    kernel = ops._axial_kernel(conv.weight, "axial_conv_block")
+    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1:
+        raise ops.StxError(f"axial_conv_block: stride {tuple(conv.stride)} dilation {tuple(conv.dilation)} groups {conv.groups}: "
+                           "only dense stride-1 convolutions are served")
+    if tuple(conv.padding) != tuple(k // 2 for k in kernel) or conv.padding_mode != "zeros":
+        raise ops.StxError(f"axial_conv_block: padding {conv.padding} ({conv.padding_mode}) is not the 'same' zero padding of kernel {kernel}")
+    return kernel
+
+
+def _fold_with_bias(conv, bn):
+    """Eval-mode BatchNorm behind a convolution WITH a bias as per-channel (scale, shift): shift = beta + (bias - running_mean) *
+    scale.  Cached on the convolution module next to (and keyed by) the BatchNorm's own folded pair."""
+    scale, shift = _fold(bn)
+    if conv.bias is None:
+        return scale, shift
+    hit = conv.__dict__.get("_stx_fold") if ops._CACHE_ENABLED else None
+    key = (conv.bias._version, conv.bias.data_ptr())
+    if hit is not None and hit[0] == key and hit[1] is shift:
+        return scale, hit[2]
+    with torch.no_grad():
+        shift_b = torch.addcmul(shift, conv.bias, scale).contiguous()
+    if ops._CACHE_ENABLED:
+        conv.__dict__["_stx_fold"] = (key, shift, shift_b)
+    return scale, shift_b
+
+
+@ops.fp32_region
+def axial_conv_block(x, conv, bn):
+    """y = ReLU(BN(conv(x) + bias)) on a dense NDHWC tensor for the (1,3,3) / (kd,1,1) convolutions of FoundationStereo's
+    Conv3dNormActReduced, in the three modes of conv_block:
+      * inference: bias and BatchNorm folded into the convolution's epilogue, one launch;
+      * train-mode BatchNorm: raw output + partial rows -> BnActFn.  The bias cancels in the normalised output; it enters
+        running_mean (mean of z plus the bias) and its gradient is returned as exact zeros (ops.ZeroGradBiasFn);
+      * eval-mode BatchNorm with autograd: the bias is added to the raw output by torch (its gradient is the channel sum)."""
+    kernel = _axial_cfg(conv)
+    if not isinstance(bn, nn.modules.batchnorm._BatchNorm):
+        raise ops.StxError(f"axial_conv_block: {type(bn).__name__} is not a BatchNorm")
+    if not _needs_grad(x, conv, bn) and not bn.training:
+        scale, shift = _fold_with_bias(conv, bn)
+        xk, wk, _ = ops._axial_prepare(x, conv.weight.detach(), "axial_conv_block")
+        wp = ops.pack_weight_axial(wk, 0, owner=conv.weight if wk.shape == conv.weight.shape else None)
+        return ops.conv3d_axial_forward(xk, wp, conv.weight.shape[0], kernel, scale, shift, None, 1)[0]
+    want = bn.training
+    z, part = ops.AxialConvRawFn.apply(x, conv.weight, want)
+    if conv.bias is not None:
+        z = ops.ZeroGradBiasFn.apply(z, conv.bias) if want else z + conv.bias
+    st = _bn_state(bn, part if want else None, z.numel() // z.shape[-1])
+    y = ops.BnActFn.apply(z, bn.weight, bn.bias, None, None, None, None, 1, st, None)
+    if want and conv.bias is not None and bn.track_running_stats and bn.running_mean is not None:
+        with torch.no_grad():                    # running_mean follows mean(z + bias); the variance does not see the bias
+            bn.running_mean.add_(conv.bias.detach(), alpha=float(st["momentum"]))
+    return y
+
+
 @ops.fp32_region
 def convbn_block(x, seq, relu=False, second=None, residual=None, mish=False, raw=None, second_raw=None):
     """`seq` = nn.Sequential(conv, bn) as built by convbn_3d (or (ConvTranspose3d, BatchNorm3d))."""

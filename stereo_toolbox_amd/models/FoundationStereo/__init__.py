@@ -1,2 +1,2 @@
-from .submodule import (build_concat_volume, build_gwc_volume, disparity_regression, groupwise_correlation,  # noqa: F401
-                        init_comb_volume)
+from .submodule import (Conv3dNormActReduced, build_concat_volume, build_gwc_volume, disparity_regression,  # noqa: F401
+                        groupwise_correlation, init_comb_volume)

@@ -9,11 +9,18 @@ models/FoundationStereo/submodule.py:388-427 and the four lines of `FoundationSt
 
 The norm of a pixel does not depend on the disparity, so the normalised volume is the plain group-wise correlation volume of the
 two normalised maps: one HBM-bound pre-pass per map (csrc/group_normalize.hip), then the MFMA builder (20 / 28 channels per
-group for the 160 / 224-channel maps of the vitb / vitl backbones, 16 for vits).  The rest of FoundationStereo (DepthAnything
-backbone, hourglass with disparity transformers, GRU updates) is outside the scope of this package; `corr_stem` etc. take the
-dense NDHWC volume of `init_comb_volume` through aggregation.conv_block like the IGEV aggregation does.
+group for the 160 / 224-channel maps of the vitb / vitl backbones, 16 for vits).
+
+Behind the volume, `Conv3dNormActReduced` -- the "axial-planar convolution" that makes up twelve layers of the reference's
+`hourglass` (foundation_stereo.py:46-124) -- runs on csrc/conv3d_axial.hip.  NOT built: the disparity transformer
+(`CostVolumeDisparityAttention`, flash attention), the composed `hourglass` / `corr_stem` / `classifier` (the classifier's
+7x7x7 convolution is another unsupported shape), the GRU update block and the DepthAnything backbone.  `corr_stem` etc. take
+the dense NDHWC volume of `init_comb_volume` through aggregation.conv_block like the IGEV aggregation does.
 """
+import torch.nn as nn
+
 from ... import ops
+from ...aggregation import axial_conv_block
 
 
 def groupwise_correlation(fea1, fea2, num_groups):
@@ -49,3 +56,57 @@ def init_comb_volume(features_left, features_right, left_tmp, right_tmp, max_dis
     (`ops.to_ncdhw` gives the reference's [B, C, D, H, W] view)."""
     return ops.cost_volume(features_left, features_right, left_tmp, right_tmp, max_disp // 4, cv_group, mask_left=False,
                            normalize=True)
+
+
+class Conv3dNormActReduced(nn.Module):
+    """reference FoundationStereo/submodule.py:89-114: Conv3d (1,k,k) + norm + ReLU, then Conv3d (kernel_disp,1,1) + norm + ReLU,
+    both convolutions with a bias -- same signature, same state-dict keys (`conv1.0.weight`, `conv1.0.bias`, `conv1.1.*`,
+    `conv2.0.*`, `conv2.1.*`), shapes and order.  The nn modules are parameter containers; the arithmetic runs on the
+    axial-planar MFMA kernels (aggregation.axial_conv_block), in fp32 also under autocast.
+
+    Served: kernel_size 3, kernel_disp odd up to 17, stride 1, norm = BatchNorm3d (SyncBatchNorm after conversion).  Anything else
+    raises StxError at construction; there is no CPU fallback.
+
+    The gradient of `conv*.0.bias` under a train-mode BatchNorm is analytically zero (the batch mean removes the bias); the
+    block returns exact zeros for it, where the reference's autograd leaves rounding noise (1e-14 in fp64).  With eval-mode
+    BatchNorm and gradients enabled it is the channel sum of the raw output's gradient."""
+
+    def __init__(self, C_in, C_out, hidden=None, kernel_size=3, kernel_disp=None, stride=1, norm=nn.BatchNorm3d):
+        super().__init__()
+        if kernel_disp is None:
+            kernel_disp = kernel_size
+        if hidden is None:
+            hidden = C_out
+        if stride != 1:
+            raise ops.StxError(f"Conv3dNormActReduced: stride {stride} is not served (stride 1 only)")
+        if kernel_size != 3:
+            raise ops.StxError(f"Conv3dNormActReduced: kernel_size {kernel_size} is not served (3 only)")
+        if kernel_disp % 2 != 1 or not 3 <= kernel_disp <= ops.AXIAL_MAX_TAPS:
+            raise ops.StxError(f"Conv3dNormActReduced: kernel_disp {kernel_disp} is not served (odd, 3..{ops.AXIAL_MAX_TAPS})")
+        if not (isinstance(norm, type) and issubclass(norm, nn.modules.batchnorm._BatchNorm)):
+            raise ops.StxError(f"Conv3dNormActReduced: norm {getattr(norm, '__name__', norm)} is not a BatchNorm")
+        if max(C_in, hidden, C_out) > ops.AXIAL_MAX_CHANNELS:
+            raise ops.StxError(f"Conv3dNormActReduced: more than {ops.AXIAL_MAX_CHANNELS} channels are not served")
+        self.conv1 = nn.Sequential(
+            nn.Conv3d(C_in, hidden, kernel_size=(1, kernel_size, kernel_size), padding=(0, kernel_size // 2, kernel_size // 2),
+                      stride=(1, stride, stride)),
+            norm(hidden),
+            nn.ReLU(),
+        )
+        self.conv2 = nn.Sequential(
+            nn.Conv3d(hidden, C_out, kernel_size=(kernel_disp, 1, 1), padding=(kernel_disp // 2, 0, 0), stride=(stride, 1, 1)),
+            norm(C_out),
+            nn.ReLU(),
+        )
+
+    def run(self, x):
+        """x: dense [B, D, H, W, C] on a ROCm device -> dense [B, D, H, W, C_out]."""
+        x = axial_conv_block(x, self.conv1[0], self.conv1[1])
+        return axial_conv_block(x, self.conv2[0], self.conv2[1])
+
+    @ops.fp32_region
+    def forward(self, x):
+        """x: logical [B, C, D, H, W] (any strides; a view of a dense NDHWC tensor costs no copy) -> logical [B, C_out, D, H, W]."""
+        if x.dim() != 5:
+            raise ops.StxError(f"Conv3dNormActReduced: expected [B, C, D, H, W], got shape {tuple(x.shape)}")
+        return ops.to_ncdhw(self.run(ops.to_ndhwc(x)))

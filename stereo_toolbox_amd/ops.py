@@ -494,6 +494,196 @@ class ConvRawFn(torch.autograd.Function):
         return gx, gw, None, None, None, None
 
 
+# ------------------------------------------------------------------- axial-planar convolutions (conv3d_axial.hip)
+AXIAL_MAX_CHANNELS = 192
+AXIAL_MAX_TAPS = 17
+
+
+def _axial_kernel(w, who):
+    """(kd, kh, kw) of a weight [Cout, Cin, kd, kh, kw] the axial-planar kernels serve: (1,3,3) or (kd,1,1), kd odd, 3..17."""
+    if w.dim() != 5:
+        raise StxError(f"{who}: expected a weight [Cout, Cin, kd, kh, kw], got shape {tuple(w.shape)}")
+    kd, kh, kw = (int(k) for k in w.shape[2:])
+    planar = (kd, kh, kw) == (1, 3, 3)
+    axial = kh == 1 and kw == 1 and kd % 2 == 1 and 3 <= kd <= AXIAL_MAX_TAPS
+    if not (planar or axial):
+        raise StxError(f"{who}: kernel {(kd, kh, kw)} is not served -- (1,3,3) or (kd,1,1) with kd odd, 3 <= kd <= {AXIAL_MAX_TAPS}")
+    if w.shape[0] > AXIAL_MAX_CHANNELS or w.shape[1] > AXIAL_MAX_CHANNELS:
+        raise StxError(f"{who}: {w.shape[1]} -> {w.shape[0]} channels, at most {AXIAL_MAX_CHANNELS} are served")
+    return kd, kh, kw
+
+
+def pack_weight_axial(w, mode, owner=None):
+    """Packed copy of a torch weight [A][B][kd,kh,kw] for stx_conv3d_axial_fwd (mode 0: forward, 1: data gradient); cached on
+    `owner` like pack_weight."""
+    _chk(w, "weight", 5)
+    kd, kh, kw = _axial_kernel(w, "pack_weight_axial")
+    if owner is not None and _CACHE_ENABLED:
+        cache = owner.__dict__.setdefault("_stx_packed", {})
+        hit = cache.get(("axial", mode))
+        if hit is not None and hit[0] == (owner._version, owner.data_ptr()):
+            return hit[1]
+    A, Bd = w.shape[0], w.shape[1]
+    K, N = (Bd, A) if mode == 0 else (A, Bd)
+    n = get_lib().raw("stx_conv3d_axial_packed_floats")(K, N, kd, kh, kw)
+    if n <= 0:
+        raise StxError(f"pack_weight_axial: GEMM-K {K} (a multiple of 4), N {N}, kernel {(kd, kh, kw)} unsupported")
+    wp = torch.empty(n, dtype=torch.float32, device=w.device)
+    _call("stx_conv3d_axial_pack_weight", _p(w), _p(wp), A, Bd, kd, kh, kw, mode)
+    if owner is not None and _CACHE_ENABLED:
+        cache[("axial", mode)] = ((owner._version, owner.data_ptr()), wp)
+    return wp
+
+
+def conv3d_axial_forward(x, wp, Cout, kernel, scale=None, bias=None, residual=None, act=0, want_stats=False):
+    """out = act(conv(x) * scale + bias + residual) for a (1,3,3) / (kd,1,1) stride-1 "same" convolution of a dense NDHWC
+    tensor; optional BatchNorm partial rows of the raw output (exactly the rows the launch writes)."""
+    _chk(x, "x", 5)
+    B, D, H, W, Cin = x.shape
+    kd, kh, kw = kernel
+    out = torch.empty(B, D, H, W, Cout, dtype=torch.float32, device=x.device)
+    stats = None
+    if want_stats:
+        rows = get_lib().raw("stx_conv3d_axial_fwd_stat_rows")(B, D, H, W, Cin, Cout, kd, kh, kw)
+        stats = torch.empty(rows, 2, Cout, dtype=torch.float32, device=x.device)
+    _call("stx_conv3d_axial_fwd", _p(x), _p(wp), _p(out), _p(scale), _p(bias), _p(residual), _p(stats), B, D, H, W, Cin, Cout,
+          kd, kh, kw, int(act))
+    return out, stats
+
+
+def conv3d_axial_wgrad(x, gz, kernel):
+    """dw [CC, CF, taps] = sum_vox x[vox + t - pad][cf] * gz[vox][cc] (fixed-order reduction of a workspace slab)."""
+    B, D, H, W, CF = x.shape
+    CC = gz.shape[-1]
+    kd, kh, kw = kernel
+    n = get_lib().raw("stx_conv3d_axial_wgrad_workspace_floats")(B, D, H, W, CF, CC, kd, kh, kw)
+    if n <= 0:
+        raise StxError(f"conv3d_axial_wgrad: {CF} x {CC} channels, kernel {kernel} unsupported")
+    ws = _WS.get("axwgrad", n, x.device)
+    dw = torch.empty(CC, CF, kd * kh * kw, dtype=torch.float32, device=x.device)
+    _call("stx_conv3d_axial_wgrad", _p(x), _p(gz), _p(dw), _p(ws), B, D, H, W, CF, CC, kd, kh, kw)
+    return dw
+
+
+def _pad4(C):
+    return (C + 3) // 4 * 4
+
+
+def _axial_prepare(x, w, who):
+    """Checks of an axial-planar call and its operands in kernel form: input channels zero-padded to a multiple of 4."""
+    _chk(x, "x", 5)
+    _chk(w, "weight", 5)
+    kernel = _axial_kernel(w, who)
+    if x.shape[-1] != w.shape[1]:
+        raise StxError(f"{who}: input has {x.shape[-1]} channels, weight expects {w.shape[1]}")
+    Cp = _pad4(w.shape[1])
+    if Cp != w.shape[1]:
+        x, w = _pad_channels(x, Cp), pad_weight_channels(w, Cp)
+    return x, w, kernel
+
+
+def _axial_backward(x, w, kernel, gz, cin_true, need_x, need_w):
+    """Data and weight gradient of z = conv(x, w) on the axial-planar kernels (x, w as _axial_prepare left them)."""
+    gz = gz.contiguous()
+    Co, Ci = w.shape[0], w.shape[1]
+    gz_k, w_k = gz, w
+    if Co % 4:                          # GEMM-K of the data gradient / the gz operand of the weight gradient in steps of 4
+        Cp = _pad4(Co)
+        gz_k = _pad_channels(gz, Cp)
+        w_k = w.new_zeros(Cp, *w.shape[1:])
+        w_k[:Co] = w
+    gx = gw = None
+    if need_x:
+        gx, _ = conv3d_axial_forward(gz_k, pack_weight_axial(w_k, 1), Ci, kernel)
+        if Ci != cin_true:
+            gx = gx[..., :cin_true].contiguous()
+    if need_w:
+        gw = conv3d_axial_wgrad(x, gz_k, kernel)[:Co, :cin_true].reshape(Co, cin_true, *kernel)
+        if not gw.is_contiguous():
+            gw = gw.contiguous()
+    return gx, gw
+
+
+class AxialConvRawFn(torch.autograd.Function):
+    """z = conv(x, w) for the (1,3,3) / (kd,1,1) stride-1 convolutions, raw output + BatchNorm partial rows -- the twin of
+    ConvRawFn on csrc/conv3d_axial.hip.  x: dense NDHWC; w: the torch parameter [Cout, Cin, kd, kh, kw].  backward = data
+    gradient (the forward kernel on flipped / transposed weights) + weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, want_stats):
+        ctx.cin_true = w.shape[1]
+        x, w, kernel = _axial_prepare(x, w, "AxialConvRawFn")
+        z, stats = conv3d_axial_forward(x, pack_weight_axial(w, 0), w.shape[0], kernel, want_stats=want_stats)
+        ctx.save_for_backward(x, w)
+        ctx.kernel = kernel
+        if stats is None:
+            stats = x.new_empty(0)
+        ctx.mark_non_differentiable(stats)
+        return z, stats
+
+    @staticmethod
+    def backward(ctx, gz, _gstats):
+        x, w = ctx.saved_tensors
+        gx, gw = _axial_backward(x, w, ctx.kernel, gz, ctx.cin_true, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, gw, None
+
+
+class _AxialConvBiasFn(torch.autograd.Function):
+    """ops.conv3d_axial with a bias under autograd: the bias rides in the forward kernel's epilogue; its gradient is the
+    channel sum of gz (a torch reduction)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        ctx.cin_true = w.shape[1]
+        x, w, kernel = _axial_prepare(x, w, "conv3d_axial")
+        z, _ = conv3d_axial_forward(x, pack_weight_axial(w, 0), w.shape[0], kernel, bias=bias.contiguous())
+        ctx.save_for_backward(x, w)
+        ctx.kernel = kernel
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        x, w = ctx.saved_tensors
+        gx, gw = _axial_backward(x, w, ctx.kernel, gz, ctx.cin_true, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        gb = gz.sum((0, 1, 2, 3)) if ctx.needs_input_grad[2] else None
+        return gx, gw, gb
+
+
+class ZeroGradBiasFn(torch.autograd.Function):
+    """z unchanged, with `bias` tied into the graph: a convolution bias in front of a batch-statistics BatchNorm cancels in the
+    output, its gradient is analytically zero -- returned as exact zeros instead of a volume-sized reduction."""
+
+    @staticmethod
+    def forward(ctx, z, bias):
+        ctx.save_for_backward(bias)
+        return z.view_as(z)
+
+    @staticmethod
+    def backward(ctx, gz):
+        (bias,) = ctx.saved_tensors
+        return gz, torch.zeros_like(bias)
+
+
+@fp32_region
+def conv3d_axial(x, weight, bias=None):
+    """Stride-1 "same" Conv3d with a (1,3,3) or (kd,1,1) kernel (kd odd, 3..17) on the gfx950 MFMA kernels, with autograd.
+    x: dense channels-last [B, D, H, W, Cin] (`to_ndhwc`); weight: [Cout, Cin, kd, kh, kw]; bias: [Cout] or None.
+    Returns [B, D, H, W, Cout].  Raises StxError for CPU tensors, non-fp32 input outside autocast, non-contiguous input and any
+    other kernel shape; there is no fallback."""
+    _chk(x, "x", 5)
+    _chk(weight, "weight", 5)
+    _chk(bias, "bias", 1)
+    _axial_kernel(weight, "conv3d_axial")
+    if bias is not None and bias.shape[0] != weight.shape[0]:
+        raise StxError(f"conv3d_axial: bias of {bias.shape[0]} for {weight.shape[0]} output channels")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
+        if bias is None:
+            return AxialConvRawFn.apply(x, weight, False)[0]
+        return _AxialConvBiasFn.apply(x, weight, bias)
+    xk, wk, kernel = _axial_prepare(x, weight.detach(), "conv3d_axial")
+    return conv3d_axial_forward(xk, pack_weight_axial(wk, 0), weight.shape[0], kernel, bias=None if bias is None else bias.detach())[0]
+
+
 class SharedInputConvsFn(torch.autograd.Function):
     """Raw outputs (+ BN partial sums) of SEVERAL plain convolutions of ONE activation -- the tensors with more than one
     convolution consumer in the reference graphs: the hourglass input (conv1 stride 2 + redir1 1x1x1, gwcnet.py:85,103) together
