@@ -166,6 +166,50 @@ long long stx_conv3d_axial_wgrad_workspace_floats(int B, int D, int H, int W, in
 int stx_conv3d_axial_wgrad(const float* x, const float* gz, float* dw, float* workspace, int B, int D, int H, int W, int CF,
                            int CC, int kd, int kh, int kw, void* stream);
 
+/* ---- ConvGRU cell (csrc/convgru.hip) ----------------------------------------------------------------
+ * The cell of the iterative families (reference IGEVStereo/update.py:25-40, the same class in RAFTStereo, DEFOMStereo,
+ * StereoAnywhere, FoundationStereo): three 3x3 convolutions (padding 1, stride 1, bias) over [h | x..] / [r h | x..] with fused
+ * sigmoid / tanh gates, exact fp32 MFMA.  Activations are channels-last fp32 [B][H][W][C].  The K axis of a convolution is a
+ * virtual concatenation of up to 4 SOURCES, each given as (device pointer, channels, pixel pitch in floats): pointer 16-byte
+ * aligned, channels a multiple of 4, pitch >= channels and a multiple of 4; unused trailing sources are (NULL, 0, 0).  Served
+ * (stx_convgru_supported(hidden, nx, cx0, cx1, cx2, kernel)): hidden a multiple of 16 up to 128, 1..3 x sources (the fourth
+ * source is h), hidden + sum cx <= 512, kernel 3.
+ * stx_convgru_pack_weight: packs one or two (w1 may be NULL) torch weights [A][Bd][3][3], stacked along A, into
+ *   stx_convgru_packed_floats(K, N) floats; mode 0: forward (K = Bd, N = A or 2 A); mode 1: data gradient (flipped taps,
+ *   transposed channels: K = A or 2 A, N = Bd).
+ * stx_convgru_gemm: acc[pix][n] = conv over the source list with packed weights of N output channels, then the epilogue `epi`:
+ *   0 raw: out0[pix][out_pitch] = acc (+ add0[pix][add0_pitch]); out0 may be add0 itself (updated in place);
+ *   1 zr:  N = 2 split (split = hidden), z | r stacked: out0 = z = sigmoid(acc + bias0 + add0) [pix][hidden],
+ *          out1 = r h with r = sigmoid(acc + bias1 + add1), out2 = r (may be NULL);
+ *   2 q:   N = split: q = tanh(acc + bias0 + add0), out0 = h' = (1 - z) h + z q, out1 = q (may be NULL).
+ *   bias / add pointers may be NULL (zero); h [pix][h_pitch] is the state at the centre pixel; outputs never alias h.
+ * stx_convgru_gate_bwd: gq = g z (1 - q^2), gz = g (q - h) z (1 - z), dense [pix][hidden]; rows (may be NULL)
+ *   [stx_convgru_gate_rows(P, hidden)][2][hidden] per-workgroup partial sums of gq | gz (the bias gradients).
+ * stx_convgru_reset_bwd: buf [pix][buf_pitch] holds g_rh in its first `hidden` channels: gr = g_rh h r (1 - r), and these
+ *   channels become g (1 - z) + g_rh r; rows (may be NULL) [stx_convgru_gate_rows][hidden] partial sums of gr.
+ * stx_convgru_row_sum: out[n] = sum of rows[nrows][n] in row order.
+ * stx_convgru_wgrad: dw[(1 or 2) CG][K][9] from the source list against the dense maps g0 (and g1, may be NULL) [pix][CG];
+ *   partial sums in `workspace` (stx_convgru_wgrad_workspace_floats(B, H, W, K, CC = rows of dw) floats), fixed-order reduction.
+ * No atomics: every result is bitwise reproducible.  Unsupported arguments return an error (the queries 0) and launch nothing. */
+int stx_convgru_supported(int hidden, int nx, int cx0, int cx1, int cx2, int ksize);
+long long stx_convgru_packed_floats(int K, int N);
+int stx_convgru_pack_weight(const float* w0, const float* w1, float* wp, int A, int Bd, int mode, void* stream);
+int stx_convgru_gemm(const float* s0, int c0, int p0, const float* s1, int c1, int p1, const float* s2, int c2, int p2,
+                     const float* s3, int c3, int p3, const float* wp, int N, int epi, int split, const float* bias0,
+                     const float* bias1, const float* add0, int add0_pitch, const float* add1, int add1_pitch, const float* h,
+                     int h_pitch, const float* z, float* out0, float* out1, float* out2, int out_pitch, int B, int H, int W,
+                     void* stream);
+int stx_convgru_gate_rows(long long P, int hidden);
+int stx_convgru_gate_bwd(const float* g, int g_pitch, const float* z, const float* q, const float* h, int h_pitch, float* gq,
+                         float* gz, float* rows, long long P, int hidden, void* stream);
+int stx_convgru_reset_bwd(float* buf, int buf_pitch, const float* g, int g_pitch, const float* z, const float* r, const float* h,
+                          int h_pitch, float* gr, float* rows, long long P, int hidden, void* stream);
+int stx_convgru_row_sum(const float* rows, float* out, int nrows, int n, void* stream);
+long long stx_convgru_wgrad_workspace_floats(int B, int H, int W, int K, int CC);
+int stx_convgru_wgrad(const float* s0, int c0, int p0, const float* s1, int c1, int p1, const float* s2, int c2, int p2,
+                      const float* s3, int c3, int p3, const float* g0, const float* g1, int CG, float* dw, float* workspace,
+                      int B, int H, int W, void* stream);
+
 /* 3x3 stride-1 Conv2d (padding 1, no bias), channels-last, of the 2-D feature CNN's BasicBlocks with 32 / 64 channels: forward
  * and data gradient (reference models/GwcNet/gwcnet.py:12-42 `convbn(in, out, 3, 1, pad, 1)` -> nn.Conv2d at 1/2 and 1/4
  * resolution; PSMNet/submodule.py:57-97; ACVNet/acv.py:15-40).  x [B][H][W][Cin], out [B][H][W][Cout], fp32.

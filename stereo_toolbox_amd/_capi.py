@@ -64,6 +64,17 @@ SIGNATURES = {
     "stx_conv3d_axial_fwd": [_P] * 7 + [_I] * 10 + [_P],
     "stx_conv3d_axial_wgrad_workspace_floats": [_I] * 9,
     "stx_conv3d_axial_wgrad": [_P, _P, _P, _P] + [_I] * 9 + [_P],
+    # convgru.hip
+    "stx_convgru_supported": [_I] * 6,
+    "stx_convgru_packed_floats": [_I, _I],
+    "stx_convgru_pack_weight": [_P, _P, _P, _I, _I, _I, _P],
+    "stx_convgru_gemm": [_P, _I, _I] * 4 + [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_convgru_gate_rows": [_L, _I],
+    "stx_convgru_gate_bwd": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _L, _I, _P],
+    "stx_convgru_reset_bwd": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _L, _I, _P],
+    "stx_convgru_row_sum": [_P, _P, _I, _I, _P],
+    "stx_convgru_wgrad_workspace_floats": [_I] * 5,
+    "stx_convgru_wgrad": [_P, _I, _I] * 4 + [_P, _P, _I, _P, _P, _I, _I, _I, _P],
     # conv2d.hip
     "stx_conv2d_supported": [_I, _I],
     "stx_conv2d_stat_rows": [_I],

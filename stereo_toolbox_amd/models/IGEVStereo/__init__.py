@@ -2,3 +2,4 @@ from .aggregation import BasicConv, FeatureAtt, IGEVCostAggregation, hourglass  
 from .geometry import Combined_Geo_Encoding_Volume  # noqa: F401
 from .submodule import (build_gwc_volume, context_upsample, disparity_regression, groupwise_correlation,  # noqa: F401
                         init_disparity, init_gwc_volume, upsample_disp_from_logits)
+from .update import ConvGRU  # noqa: F401

@@ -684,6 +684,271 @@ def conv3d_axial(x, weight, bias=None):
     return conv3d_axial_forward(xk, pack_weight_axial(wk, 0), weight.shape[0], kernel, bias=None if bias is None else bias.detach())[0]
 
 
+# ------------------------------------------------------------------------------ ConvGRU cell (convgru.hip)
+CONVGRU_MAX_HIDDEN = 128
+CONVGRU_MAX_K = 512
+CONVGRU_MAX_X = 3            # a launch takes 4 sources: h (or r h) and up to three x
+CONVGRU_PACKS = 0            # pack launches so far (tests: a training step packs once per weight and mode, not once per iteration)
+
+
+def _cl_pitch(t):
+    """Pixel pitch in floats if the memory of the logical NCHW tensor `t` is channels-last [B][H][W][pitch >= C] the kernels can
+    read in place (a channel slice of a wider map included), else None."""
+    B, C, H, W = t.shape
+    sb, sc, sh, sw = t.stride()
+    if C > 1 and sc != 1:
+        return None
+    pitch = sw if W > 1 else (sh if H > 1 else (sb if B > 1 else C))      # (the stride of a size-1 dim says nothing)
+    if pitch < C or pitch % 4 or t.data_ptr() % 16:
+        return None
+    if (W > 1 and sw != pitch) or (H > 1 and sh != W * pitch) or (B > 1 and sb != H * W * pitch):
+        return None
+    return pitch
+
+
+def _cl_source(t):
+    """(tensor, pitch) of a logical NCHW tensor for the channels-last kernels: in place where its memory allows, else one copy."""
+    pitch = _cl_pitch(t)
+    if pitch is None:
+        t = t.contiguous(memory_format=torch.channels_last)
+        pitch = _cl_pitch(t)
+        if pitch is None:                                    # (size-1 dims leave the strides of the copy unspecified)
+            t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+            pitch = t.shape[1]
+    return t, pitch
+
+
+def _convgru_chk(t, name, like=None, channels=None):
+    if t is None:
+        return
+    if not on_device(t):
+        raise StxError(f"convgru: {name}: expected a ROCm device tensor, got {t.device} -- the cell has no CPU fallback")
+    if t.dtype != torch.float32:
+        raise StxError(f"convgru: {name}: expected float32, got {t.dtype}")
+    if like is not None:
+        if t.dim() != 4 or t.shape[0] != like.shape[0] or tuple(t.shape[2:]) != tuple(like.shape[2:]):
+            raise StxError(f"convgru: {name} has shape {tuple(t.shape)}, h has {tuple(like.shape)} (batch, H and W must agree)")
+        if channels is not None and t.shape[1] != channels:
+            raise StxError(f"convgru: {name} has {t.shape[1]} channels, expected {channels}")
+
+
+def _convgru_pack(w0, w1, mode):
+    """Packed copy of one or two ConvGRU weights [hidden][K][3][3] (mode 0: forward, 1: data gradient); cached on `w0` under
+    the rules of set_weight_cache, keyed by the versions and addresses of both."""
+    global CONVGRU_PACKS
+    key = tuple(v for w in (w0, w1) if w is not None for v in (w._version, w.data_ptr()))
+    tag = ("convgru", mode, w1 is not None)
+    if _CACHE_ENABLED:
+        cache = w0.__dict__.setdefault("_stx_packed", {})
+        hit = cache.get(tag)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+    A, Bd = w0.shape[0], w0.shape[1]
+    nw = 1 if w1 is None else 2
+    K, N = (Bd, nw * A) if mode == 0 else (nw * A, Bd)
+    n = get_lib().raw("stx_convgru_packed_floats")(K, N)
+    if n <= 0:
+        raise StxError(f"convgru: GEMM-K {K} (a multiple of 4, <= {CONVGRU_MAX_K}) x N {N} unsupported")
+    wp = torch.empty(n, dtype=torch.float32, device=w0.device)
+    w0c, w1c = w0.detach().contiguous(), None if w1 is None else w1.detach().contiguous()
+    _call("stx_convgru_pack_weight", _p(w0c), _p(w1c), _p(wp), A, Bd, mode)
+    CONVGRU_PACKS += 1
+    if _CACHE_ENABLED:
+        cache[tag] = (key, wp)
+    return wp
+
+
+def _src_args(srcs):
+    """The flat (pointer, channels, pitch) x 4 form of a source list [(tensor NCHW-logical, pitch)]."""
+    out = []
+    for t, pitch in srcs:
+        out += [_p(t), t.shape[1], pitch]
+    for _ in range(4 - len(srcs)):
+        out += [None, 0, 0]
+    return out
+
+
+def convgru_gemm(srcs, wp, N, B, H, W, epi=0, split=0, bias0=None, bias1=None, add0=None, add1=None, h=None, z=None, out0=None,
+                 out1=None, out2=None, out_pitch=0):
+    """One launch of the ConvGRU implicit-GEMM kernel (include/stx_hip.h: stx_convgru_gemm).  srcs / add0 / add1 / h:
+    (tensor, pitch) pairs or None."""
+    a0, a0p = add0 if add0 is not None else (None, 0)
+    a1, a1p = add1 if add1 is not None else (None, 0)
+    ht, hp = h if h is not None else (None, 0)
+    _call("stx_convgru_gemm", *_src_args(srcs), _p(wp), N, epi, split, _p(bias0), _p(bias1), _p(a0), a0p, _p(a1), a1p, _p(ht), hp,
+          _p(z), _p(out0), _p(out1), _p(out2), out_pitch, B, H, W)
+
+
+def _nchw(t):
+    """Logical NCHW view of a dense channels-last buffer [B][H][W][C] (or of a channel slice of one)."""
+    return t.permute(0, 3, 1, 2)
+
+
+class ConvGRUFn(torch.autograd.Function):
+    """h' = ConvGRU(h, cz, cr, cq, x..) as one node on csrc/convgru.hip.  Forward: the zr launch and the q launch.  Backward: gate
+    backward, data gradient of the q convolution, reset backward, data gradient of the z and r convolutions with the running
+    [dL/dh | g_x] as addend, two weight gradients and the bias-row sums; nothing is accumulated by autograd afterwards.
+    Saved: h and the x sources by reference, z, r, q and r h (4 x pixels x hidden floats per call)."""
+
+    @staticmethod
+    def forward(ctx, h, cz, cr, cq, wz, bz, wr, br, wq, bq, *xs):
+        B, hidden, H, W = h.shape
+        dev = h.device
+        need = any(ctx.needs_input_grad)                      # (all False under no_grad: r and q are then not written)
+        hs = _cl_source(h.detach())
+        xsrc = [_cl_source(x.detach()) for x in xs]
+        cs = [None if c is None else _cl_source(c.detach()) for c in (cz, cr, cq)]
+        new = lambda: torch.empty(B, H, W, hidden, dtype=torch.float32, device=dev)       # noqa: E731
+        z, rh, hn = new(), new(), new()
+        r = new() if need else None
+        q = new() if need else None
+        bzc, brc, bqc = (None if b is None else b.detach().contiguous() for b in (bz, br, bq))
+        convgru_gemm([hs] + xsrc, _convgru_pack(wz, wr, 0), 2 * hidden, B, H, W, epi=1, split=hidden, bias0=bzc, bias1=brc,
+                     add0=cs[0], add1=cs[1], h=hs, out0=z, out1=rh, out2=r)
+        convgru_gemm([(_nchw(rh), hidden)] + xsrc, _convgru_pack(wq, None, 0), hidden, B, H, W, epi=2, split=hidden, bias0=bqc,
+                     add0=cs[2], h=hs, z=z, out0=hn, out1=q)
+        if need:
+            ctx.save_for_backward(hs[0], z, r, q, rh, wz, wr, wq, *[t for t, _ in xsrc])
+            ctx.pitches = (hs[1], [p for _, p in xsrc])
+            ctx.has_c = [c is not None for c in (cz, cr, cq)]
+            ctx.has_b = [b is not None for b in (bz, br, bq)]
+        return _nchw(hn)
+
+    @staticmethod
+    def backward(ctx, g):
+        h, z, r, q, rh, wz, wr, wq, *xt = ctx.saved_tensors
+        hp, xp = ctx.pitches
+        B, hidden, H, W = h.shape
+        dev = h.device
+        P = B * H * W
+        need = ctx.needs_input_grad
+        need_x = any(need[10:])
+        need_w = any(need[i] for i in (4, 6, 8))
+        need_b = any(need[i] for i in (5, 7, 9)) and any(ctx.has_b)
+        cx = [t.shape[1] for t in xt]
+        K = hidden + sum(cx)
+        Ndg = K if need_x else hidden                         # data gradients: [g_rh | g_x], or g_rh alone when no x wants one
+        gt, gp = _cl_source(g)
+        new = lambda: torch.empty(B, H, W, hidden, dtype=torch.float32, device=dev)       # noqa: E731
+        gq, gz, gr = new(), new(), new()
+        nrows = get_lib().raw("stx_convgru_gate_rows")(P, hidden)
+        rows_g = torch.empty(nrows, 2, hidden, dtype=torch.float32, device=dev) if need_b else None
+        rows_r = torch.empty(nrows, hidden, dtype=torch.float32, device=dev) if need_b else None
+        _call("stx_convgru_gate_bwd", _p(gt), gp, _p(z), _p(q), _p(h), hp, _p(gq), _p(gz), _p(rows_g), P, hidden)
+        buf = torch.empty(B, H, W, Ndg, dtype=torch.float32, device=dev)
+        if need_x:
+            wq1, wzr1 = _convgru_pack(wq, None, 1), _convgru_pack(wz, wr, 1)
+        else:                                                 # (a pack is laid out for its own N: the h columns alone)
+            wq1, wzr1 = _convgru_pack_head(wq, None, hidden), _convgru_pack_head(wz, wr, hidden)
+        convgru_gemm([(_nchw(gq), hidden)], wq1, Ndg, B, H, W, out0=buf, out_pitch=Ndg)
+        _call("stx_convgru_reset_bwd", _p(buf), Ndg, _p(gt), gp, _p(z), _p(r), _p(h), hp, _p(gr), _p(rows_r), P, hidden)
+        convgru_gemm([(_nchw(gz), hidden), (_nchw(gr), hidden)], wzr1, Ndg, B, H, W, add0=(buf, Ndg), out0=buf, out_pitch=Ndg)
+        grads = [None] * len(need)
+        if need[0]:
+            grads[0] = _nchw(buf[..., :hidden])
+        for i, (gc, has) in enumerate(zip((gz, gr, gq), ctx.has_c)):
+            if has and need[1 + i]:
+                grads[1 + i] = _nchw(gc)
+        off = hidden
+        for i, c in enumerate(cx):
+            if need[10 + i]:
+                grads[10 + i] = _nchw(buf[..., off:off + c])
+            off += c
+        if need_w:
+            xsrc = list(zip(xt, xp))
+            if need[4] or need[6]:
+                dzr = _convgru_wgrad([(h, hp)] + xsrc, gz, gr, B, H, W)
+                if need[4]:
+                    grads[4] = dzr[:hidden].view(hidden, K, 3, 3)
+                if need[6]:
+                    grads[6] = dzr[hidden:].view(hidden, K, 3, 3)
+            if need[8]:
+                grads[8] = _convgru_wgrad([(_nchw(rh), hidden)] + xsrc, gq, None, B, H, W).view(hidden, K, 3, 3)
+        if need_b:
+            sums = torch.empty(3, hidden, dtype=torch.float32, device=dev)         # gq | gz | gr
+            _call("stx_convgru_row_sum", _p(rows_g), _p(sums), nrows, 2 * hidden)
+            _call("stx_convgru_row_sum", _p(rows_r), _p(sums[2]), nrows, hidden)
+            for i, k in ((5, 1), (7, 2), (9, 0)):
+                if need[i] and ctx.has_b[(i - 5) // 2]:
+                    grads[i] = sums[k]
+        return tuple(grads)
+
+
+def _convgru_pack_head(w0, w1, n_out):
+    """Mode-1 packed weights restricted to the first `n_out` output channels (the data gradient of h alone, when no x source
+    wants a gradient); cached like the full pack."""
+    global CONVGRU_PACKS
+    key = tuple(v for w in (w0, w1) if w is not None for v in (w._version, w.data_ptr()))
+    tag = ("convgru_head", n_out, w1 is not None)
+    if _CACHE_ENABLED:
+        cache = w0.__dict__.setdefault("_stx_packed", {})
+        hit = cache.get(tag)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+    w0h = w0.detach()[:, :n_out].contiguous()
+    w1h = None if w1 is None else w1.detach()[:, :n_out].contiguous()
+    A = w0h.shape[0]
+    nw = 1 if w1 is None else 2
+    wp = torch.empty(get_lib().raw("stx_convgru_packed_floats")(nw * A, n_out), dtype=torch.float32, device=w0.device)
+    _call("stx_convgru_pack_weight", _p(w0h), _p(w1h), _p(wp), A, n_out, 1)
+    CONVGRU_PACKS += 1
+    if _CACHE_ENABLED:
+        cache[tag] = (key, wp)
+    return wp
+
+
+def _convgru_wgrad(srcs, g0, g1, B, H, W):
+    """dW [(1 or 2) hidden][K][9] of the source list against one or two dense gradient maps [B][H][W][hidden]."""
+    CG = g0.shape[-1]
+    K = sum(t.shape[1] for t, _ in srcs)
+    CC = CG if g1 is None else 2 * CG
+    n = get_lib().raw("stx_convgru_wgrad_workspace_floats")(B, H, W, K, CC)
+    if n <= 0:
+        raise StxError(f"convgru: weight gradient of {K} x {CC} channels unsupported")
+    ws = _WS.get("convgru_wgrad", n, g0.device)
+    dw = torch.empty(CC, K, 9, dtype=torch.float32, device=g0.device)
+    _call("stx_convgru_wgrad", *_src_args(srcs), _p(g0), _p(g1), CG, _p(dw), _p(ws), B, H, W)
+    return dw
+
+
+@fp32_region
+def convgru(h, cz, cr, cq, x_list, wz, bz, wr, br, wq, bq):
+    """The ConvGRU cell of the iterative families (reference IGEVStereo/update.py:25-40) on the gfx950 kernels, one autograd node:
+        z = sigmoid(conv(wz, [h, x..]) + bz + cz),  r = sigmoid(conv(wr, [h, x..]) + br + cr),
+        q = tanh(conv(wq, [r h, x..]) + bq + cq),   h' = (1 - z) h + z q.
+    h, cz, cr, cq: logical NCHW [B, hidden, H, W] (each c* may be None = zero); x_list: 1..3 tensors [B, C_i, H, W]; weights
+    [hidden, hidden + sum C_i, 3, 3], biases [hidden] or None.  Tensors whose memory is channels-last -- channel slices of a
+    wider channels-last map included -- are read in place, others are converted once.  Returns h' as an NCHW view of
+    channels-last storage, fp32 (under autocast: the fp32 path on the cast-up inputs).  Served: hidden a multiple of 16 up to
+    128, every C_i a multiple of 4, hidden + sum C_i <= 512; anything else raises StxError and launches nothing."""
+    x_list = list(x_list)
+    if h is None or h.dim() != 4:
+        raise StxError("convgru: h must be a tensor [B, hidden, H, W]")
+    _convgru_chk(h, "h")
+    B, hidden, H, W = h.shape
+    if not 1 <= len(x_list) <= CONVGRU_MAX_X:
+        raise StxError(f"convgru: {len(x_list)} x sources; 1..{CONVGRU_MAX_X} are served (4 sources with h)")
+    for i, x in enumerate(x_list):
+        _convgru_chk(x, f"x[{i}]", like=h)
+    for name, c in (("cz", cz), ("cr", cr), ("cq", cq)):
+        _convgru_chk(c, name, like=h, channels=hidden)
+    cx = [int(x.shape[1]) for x in x_list]
+    K = hidden + sum(cx)
+    for name, w, b in (("wz", wz, bz), ("wr", wr, br), ("wq", wq, bq)):
+        _convgru_chk(w, name)
+        _convgru_chk(b, "bias of " + name)
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+            raise StxError(f"convgru: {name} has shape {tuple(w.shape)}; only 3x3 kernels are served")
+        if tuple(w.shape[:2]) != (hidden, K):
+            raise StxError(f"convgru: {name} has shape {tuple(w.shape)}, expected {(hidden, K, 3, 3)}")
+        if b is not None and tuple(b.shape) != (hidden,):
+            raise StxError(f"convgru: bias of {name} has shape {tuple(b.shape)}, expected {(hidden,)}")
+    if not get_lib().raw("stx_convgru_supported")(hidden, len(cx), *(cx + [0] * (3 - len(cx))), 3):
+        raise StxError(f"convgru: hidden {hidden} (a multiple of 16, <= {CONVGRU_MAX_HIDDEN}) with x channels {cx} (multiples of 4, "
+                       f"hidden + sum <= {CONVGRU_MAX_K}) is not served")
+    return ConvGRUFn.apply(h, cz, cr, cq, wz, bz, wr, br, wq, bq, *x_list)
+
+
 class SharedInputConvsFn(torch.autograd.Function):
     """Raw outputs (+ BN partial sums) of SEVERAL plain convolutions of ONE activation -- the tensors with more than one
     convolution consumer in the reference graphs: the hourglass input (conv1 stride 2 + redir1 1x1x1, gwcnet.py:85,103) together
