@@ -25,7 +25,7 @@ extern "C" {
 const char* stx_last_error(void);
 const char* stx_build_info(void);
 /* Tuning / A-B switches (names = their environment variables, e.g. "STX_MARCH_BS"; list and defaults: StxTune in
- * csrc/stx_common.h).  The environment is read ONCE, when the library is loaded; stx_set_tuning changes a switch for the
+ * csrc/stx_common.h, and STX_DA_GRID in csrc/stx_runtime.hip).  The environment is read ONCE, when the library is loaded; stx_set_tuning changes a switch for the
  * calls that follow in this process (tests, tools/kernel_bench.py).  None changes a result beyond fp32 rounding.
  * stx_get_tuning: value, or -1 for an unknown name;  stx_set_tuning: 0, or 1 for an unknown name. */
 int stx_get_tuning(const char* name);
@@ -619,6 +619,41 @@ int stx_sttr_attn_fwd(const float* q, const float* k, const float* v, const floa
 int stx_sttr_attn_bwd(const float* dO, const float* dRaw, const float* q, const float* k, const float* v, const float* Qr,
                       const float* Kr, const float* o, const float* stats, int causal, float* dq, float* dk, float* dv, float* dQr,
                       float* dKr, float* scratch, long long scratch_floats, int nb, int W, int B, int E, int head_dim, void* stream);
+
+/* ---- disp_attention.hip: FoundationStereo's disparity transformer (models/FoundationStereo/submodule.py
+ * `CostVolumeDisparityAttention`): `layers` post-norm encoder layers over N sequences of L tokens x C channels, fp32.
+ * Sequences are addressed in place: the floats of token t of sequence n start at
+ *   (n / hw) * sb + (n % hw) * sp + t * st,  the C channels contiguous
+ * (dense [B][D][H][W][C]: N = B H W, L = D, hw = H W, sb = D H W C, sp = C, st = H W C; [N][L][C]: hw = 1, sb = L C, sp = 0,
+ * st = C); x, y, gy and gx of a call share one such view; base pointers 16-byte aligned, strides multiples of 4.
+ * params / gparams: HOST arrays of 16 * layers device pointers, per layer in state-dict order: q_proj.weight [C][C], q_proj.bias,
+ * k_proj.*, v_proj.*, out_proj.*, linear1.weight [F][C], linear1.bias [F], linear2.weight [C][F], linear2.bias [C], norm1.weight,
+ * norm1.bias, norm2.weight, norm2.bias.  A NULL entry of gparams is a frozen tensor: its products are skipped.
+ * Served (stx_disp_attention_supported returns 1): 1 <= L <= 32; C and F multiples of 4 up to 32; nhead divides C with
+ * C / nhead <= 8; 1 <= layers <= 8; also N L C < 2^31.  Anything else is an error and nothing is launched.
+ * Layer: Q, K, V = x W^T + b; per head softmax(Q K^T / sqrt(hd)) V; z = x + drop(out_proj(.)); x1 = LayerNorm(z) (eps, biased
+ * variance); y = LayerNorm(x1 + drop(linear2(drop(gelu(linear1(x1)))))), exact erf GELU.  pe (NULL or [L][C]) is added to x once in
+ * front.  Soft-max, erf and the LayerNorm moments are formed in double and rounded once.
+ * Dropout: seed is a DEVICE pointer to one 64-bit integer (NULL or p == 0: nothing is drawn), p the probability as fp32.
+ *   Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (n, t >> 2, 4 * layer + site, channel), site 0 behind
+ *   out_proj, 1 behind the GELU (F channels), 2 behind linear2; element (layer, site, n, t, channel) is kept iff word (t & 3) of
+ *   the result is >= floor((double)p * 2^32); kept values are multiplied by (float)(1 / (1 - (double)p)).  No mask is stored: the
+ *   backward draws it again.  stx_disp_attention_masks writes the keep decisions (1 / 0) of a call as bytes
+ *   [layers][3][N][L][max(C, F)] (every channel below max(C, F) of every site).
+ * stx_disp_attention_fwd: one launch; saved (NULL or [layers][N][L][C]) receives the input of every layer, all the backward needs.
+ * stx_disp_attention_bwd: one launch per layer plus a reduction launch, from the last layer down to the lowest one anything is
+ *   wanted from; gx may be NULL; gbuf [N][L][C] carries the gradient between layers (may be NULL for one layer); workspace of
+ *   stx_disp_attention_bwd_workspace_floats(N, L, C, F) floats (0: not served): one row of parameter gradients per unit of four
+ *   consecutive sequences, added in unit order.  No float atomics; the bits do not depend on the grid (switch STX_DA_GRID). */
+int stx_disp_attention_supported(int L, int C, int nhead, int F, int layers);
+int stx_disp_attention_fwd(const float* x, const float* pe, const float* const* params, float* y, float* saved, const long long* seed,
+                           float p, float eps, int N, int L, int C, int nhead, int F, int layers, int hw, long long sb, long long sp,
+                           long long st, void* stream);
+long long stx_disp_attention_bwd_workspace_floats(int N, int L, int C, int F);
+int stx_disp_attention_bwd(const float* gy, const float* saved, const float* const* params, float* const* gparams, float* gx, float* gbuf,
+                           float* workspace, long long workspace_floats, const long long* seed, float p, float eps, int N, int L, int C,
+                           int nhead, int F, int layers, int hw, long long sb, long long sp, long long st, void* stream);
+int stx_disp_attention_masks(const long long* seed, float p, unsigned char* masks, int N, int L, int C, int F, int layers, void* stream);
 
 /* ---- convex_upsample.hip: convex upsampling with the soft-max fused, and the trainer's sequence loss; fp32 tensors -------------
  * RAFT layout (upsample_flow of RAFTStereo / DEFOMStereo, convex_upflow of StereoAnywhere, upsample_disp of SelectiveRAFT):

@@ -165,6 +165,12 @@ SIGNATURES = {
     # sttr_attention.hip
     "stx_sttr_attn_fwd": [_P] * 5 + [_I] + [_P] * 4 + [_I, _I, _I, _I, _P],
     "stx_sttr_attn_bwd": [_P] * 9 + [_I] + [_P] * 6 + [_L, _I, _I, _I, _I, _I, _P],
+    # disp_attention.hip
+    "stx_disp_attention_supported": [_I] * 5,
+    "stx_disp_attention_fwd": [_P] * 6 + [_F, _F] + [_I] * 7 + [_L, _L, _L, _P],
+    "stx_disp_attention_bwd_workspace_floats": [_I] * 4,
+    "stx_disp_attention_bwd": [_P] * 7 + [_L, _P, _F, _F] + [_I] * 7 + [_L, _L, _L, _P],
+    "stx_disp_attention_masks": [_P, _F, _P, _I, _I, _I, _I, _I, _P],
     # convex_upsample.hip
     "stx_convex_upsample_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "stx_convex_upsample_bwd_workspace_floats": [_I, _I, _I, _I],

@@ -3416,3 +3416,167 @@ def sttr_rel_attention(q, k, v, q_r=None, k_r=None, causal=False, need_raw=False
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in args[:5]):
         return SttrRelAttentionFn.apply(*args)
     return SttrRelAttentionFn.forward(_NoCtx(), *args)
+
+
+# --------------------------------------------------------------------------------------- FoundationStereo disparity transformer
+DISP_ATTN_MAX_L = 32                                                     # csrc/disp_attention.hip DA_MAX_L
+DISP_ATTN_MAX_C = 32                                                     # ... DA_MAX_C (channels and feed-forward width)
+DISP_ATTN_MAX_HEAD_DIM = 8                                               # ... DA_MAX_HD
+DISP_ATTN_MAX_LAYERS = 8                                                 # ... DA_MAX_LAYERS
+DISP_ATTN_TENSORS = 16                                                   # tensors of one layer, state-dict order
+DISP_ATTN_SITES = 3                                                      # dropout sites of one layer
+
+
+def disp_attention_served(C, nhead, F, layers=1, L=1):
+    """The rule of stx_disp_attention_supported, for checks at construction (no library needed)."""
+    ok = lambda n, top: isinstance(n, int) and 4 <= n <= top and n % 4 == 0                     # noqa: E731
+    return (ok(C, DISP_ATTN_MAX_C) and ok(F, DISP_ATTN_MAX_C) and isinstance(nhead, int) and nhead >= 1 and C % nhead == 0
+            and C // nhead <= DISP_ATTN_MAX_HEAD_DIM and 1 <= layers <= DISP_ATTN_MAX_LAYERS and 1 <= L <= DISP_ATTN_MAX_L)
+
+
+def _da_view(x):
+    """(N, L, C, hw, sb, sp, st) of a dense [B, D, H, W, C] volume or a dense [N, L, C] tensor: include/stx_hip.h."""
+    if x.dim() == 5:
+        B, D, H, W, C = x.shape
+        return B * H * W, D, C, H * W, D * H * W * C, C, H * W * C
+    N, L, C = x.shape
+    return N, L, C, 1, L * C, 0, C
+
+
+def _da_layer_shapes(C, F):
+    return [(C, C), (C,)] * 4 + [(F, C), (F,), (C, F), (C,)] + [(C,)] * 4
+
+
+def _da_seed(who, seed, like):
+    if seed is None:
+        return None
+    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != like.device:
+        raise StxError(f"{who}: seed must be a one-element int64 tensor on {like.device}, got {seed!r}")
+    return seed.contiguous()
+
+
+class DispAttentionFn(torch.autograd.Function):
+    """stx_disp_attention_fwd / _bwd: all layers as one node.  Saved: the input of every layer [layers, N, L, C], the parameters
+    and the seed by reference.  The dropout masks are drawn again in the backward from the same seed tensor."""
+
+    @staticmethod
+    def forward(ctx, x, pe, seed, cfg, *params):
+        nhead, F, layers, p, eps = cfg
+        N, L, C, hw, sb, sp, st = _da_view(x)
+        need = not isinstance(ctx, _NoCtx) and any(ctx.needs_input_grad)
+        y = torch.empty_like(x)
+        saved = torch.empty(layers, N, L, C, dtype=torch.float32, device=x.device) if need else None
+        prm = [t.detach() for t in params]
+        _call("stx_disp_attention_fwd", _p(x), _p(pe), _pointer_table(prm), _p(y), _p(saved), _p(seed), p, eps, N, L, C, nhead, F,
+              layers, hw, sb, sp, st)
+        if need:
+            ctx.save_for_backward(saved, seed, *params)
+            ctx.cfg = cfg
+            ctx.form = tuple(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        saved, seed, *params = ctx.saved_tensors
+        nhead, F, layers, p, eps = ctx.cfg
+        gy = gy.contiguous()
+        N, L, C, hw, sb, sp, st = _da_view(gy)
+        dev = gy.device
+        need = ctx.needs_input_grad
+        gx = torch.empty(ctx.form, dtype=torch.float32, device=dev) if need[0] else None
+        grads = [torch.empty_like(t) if n else None for t, n in zip(params, need[4:])]
+        if gx is None and not any(g is not None for g in grads):
+            return (None,) * len(need)
+        gbuf = torch.empty(N, L, C, dtype=torch.float32, device=dev) if layers > 1 else None
+        n = get_lib().raw("stx_disp_attention_bwd_workspace_floats")(N, L, C, F)
+        ws = _WS.get("disp_attention", n, dev)
+        prm = [t.detach() for t in params]
+        _call("stx_disp_attention_bwd", _p(gy), _p(saved), _pointer_table(prm), _pointer_table(grads), _p(gx), _p(gbuf), _p(ws), n,
+              _p(seed), p, eps, N, L, C, nhead, F, layers, hw, sb, sp, st)
+        return (gx, None, None, None, *grads)
+
+
+def _disp_attention_args(who, x, pe, params, nhead, p, seed, training):
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 5):
+        raise StxError(f"{who}: x must be a dense [B, D, H, W, C] volume or [N, L, C], got "
+                       f"{tuple(x.shape) if isinstance(x, torch.Tensor) else x!r}")
+    if not on_device(x):
+        raise StxError(f"{who}: expected a ROCm device tensor, got {x.device} -- there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise StxError(f"{who}: expected float32, got {x.dtype}")
+    x = x.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()                                         # (a slice that starts off a 16-byte boundary: the kernel loads float4)
+    params = list(params)
+    N, L, C, hw, sb, sp, st = _da_view(x)
+    if len(params) % DISP_ATTN_TENSORS or not params:
+        raise StxError(f"{who}: {len(params)} parameter tensors; {DISP_ATTN_TENSORS} per layer are expected")
+    layers = len(params) // DISP_ATTN_TENSORS
+    w1 = params[8]
+    F = int(w1.shape[0]) if isinstance(w1, torch.Tensor) and w1.dim() == 2 else -1
+    nhead = int(nhead)
+    if F < 0 or nhead < 1 or not get_lib().raw("stx_disp_attention_supported")(L, C, nhead, F, layers):
+        raise StxError(f"{who}: L={L}, C={C}, {nhead} heads, feed-forward {F}, {layers} layers is not served (L 1..{DISP_ATTN_MAX_L}; C "
+                       f"and feed-forward multiples of 4 up to {DISP_ATTN_MAX_C}; head dim <= {DISP_ATTN_MAX_HEAD_DIM}; "
+                       f"1..{DISP_ATTN_MAX_LAYERS} layers)")
+    if N < 1 or N * L * C >= 2 ** 31:
+        raise StxError(f"{who}: {N} sequences of {L} x {C}: N L C must lie in 1 .. 2^31 - 1")
+    shapes = _da_layer_shapes(C, F) * layers
+    dense = []
+    for i, (t, shape) in enumerate(zip(params, shapes)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise StxError(f"{who}: parameter {i % DISP_ATTN_TENSORS} of layer {i // DISP_ATTN_TENSORS} must be {shape}, got "
+                           f"{tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
+        if t.dtype != torch.float32 or t.device != x.device:
+            raise StxError(f"{who}: parameter {i} must be float32 on {x.device}, got {t.dtype} on {t.device}")
+        dense.append(t if t.is_contiguous() else t.contiguous())
+    if pe is not None:
+        if not isinstance(pe, torch.Tensor) or tuple(pe.shape) != (L, C) or pe.dtype != torch.float32 or pe.device != x.device:
+            raise StxError(f"{who}: pe must be a float32 [{L}, {C}] table on {x.device}")
+        pe = pe.detach().contiguous()
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise StxError(f"{who}: dropout probability {p} outside [0, 1)")
+    seed = _da_seed(who, seed, x)
+    if not training or p == 0.0:
+        p, seed = 0.0, None
+    elif seed is None:
+        raise StxError(f"{who}: training with p = {p} needs a seed tensor")
+    return x, pe, dense, nhead, F, layers, p, seed
+
+
+@fp32_region
+def disp_attention(x, pe, params, nhead, p=0.0, seed=None, training=False, eps=1e-5):
+    """FoundationStereo's disparity transformer (reference FoundationStereo/submodule.py `CostVolumeDisparityAttention`) on
+    csrc/disp_attention.hip, one autograd node: x + pe, then len(params) / 16 post-norm encoder layers
+        a = softmax(Q K^T / sqrt(hd)) V per head;  x1 = LayerNorm(x + drop(out_proj(a)));
+        y = LayerNorm(x1 + drop(linear2(drop(gelu(linear1(x1))))))
+    over the sequences of x: a dense channels-last volume [B, D, H, W, C] (one sequence of D tokens per pixel, read in place) or
+    [N, L, C].  pe: None or a [L, C] table.  params: 16 tensors per layer in state-dict order (q/k/v/out_proj weight and bias,
+    linear1, linear2, norm1, norm2).  training with p > 0 draws the three dropout masks of every layer inside the kernel from
+    `seed`, a one-element int64 tensor on x's device (never read on the host; counter layout in include/stx_hip.h); the backward
+    draws them again.  eval, or p = 0: nothing is drawn and seed may be None.  Returns a tensor of x's shape, fp32.
+    Served: L <= 32, C and the feed-forward width multiples of 4 up to 32, head dim <= 8, at most 8 layers; anything else raises
+    StxError and launches nothing."""
+    who = "disp_attention"
+    x, pe, dense, nhead, F, layers, p, seed = _disp_attention_args(who, x, pe, params, nhead, p, seed, training)
+    cfg = (nhead, F, layers, p, float(eps))
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in dense)):
+        return DispAttentionFn.apply(x, pe, seed, cfg, *dense)
+    return DispAttentionFn.forward(_NoCtx(), x, pe, seed, cfg, *dense)
+
+
+def disp_attention_masks(seed, p, N, L, C, F, layers):
+    """The keep decisions (1 / 0) `disp_attention` makes with this seed and p, as uint8 [layers, 3, N, L, max(C, F)]: site 0 behind
+    out_proj (C channels), 1 behind the GELU (F channels), 2 behind linear2 (C channels)."""
+    who = "disp_attention_masks"
+    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() != 1:
+        raise StxError(f"{who}: seed must be a one-element int64 tensor, got {seed!r}")
+    if not on_device(seed):
+        raise StxError(f"{who}: expected a ROCm device tensor, got {seed.device} -- there is no CPU fallback")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise StxError(f"{who}: dropout probability {p} outside [0, 1)")
+    out = torch.empty(layers, DISP_ATTN_SITES, N, L, max(C, F), dtype=torch.uint8, device=seed.device)
+    _call("stx_disp_attention_masks", _p(seed.contiguous()), p, _p(out), N, L, C, F, layers)
+    return out
