@@ -8,6 +8,10 @@ import ctypes
 import pytest
 import torch
 
+BAND_MIN = 4096                 # floats: the least length of a guard band of Backend.banded
+SENTINEL_BITS = 0x5EA1BA9D      # a finite float (5.8e18): the guard bands of a buffer a kernel writes
+NAN_BITS = 0x7FC00000           # the guard bands of a buffer a kernel reads
+
 
 class Backend:
     def __init__(self, name):
@@ -39,6 +43,35 @@ class Backend:
         else:
             t.zero_()
         return t
+
+    def banded(self, *shape, fill=float("nan"), nan_bands=False):
+        """(view, check): a dense fp32 view of `shape`, filled with `fill`, cut from the middle of ONE larger allocation, and a
+        `check(what)` asserting that the guard band in front of it and the one behind it still hold their bit pattern -- an
+        out-of-bounds WRITE of the kernel under test lands there, not in allocator padding or a neighbouring tensor.  Both bands
+        are multiples of 128 floats (the view keeps the allocation's 512-byte alignment, which every product tensor has), at least
+        one row of the view (its last two extents; none for a 1-D workspace) and at least 4096 floats long.  The bands hold a finite sentinel
+        (buffers a kernel writes) or, with `nan_bands`, NaN (buffers it reads: a READ past either end that reaches an output
+        poisons it).  Only memory of this allocation is ever inspected."""
+        n = 1
+        for s in shape:
+            n *= int(s)
+        row = int(shape[-1]) * int(shape[-2]) if len(shape) > 1 else 0         # a 1-D buffer has no rows: the least band
+        band = (max(row, BAND_MIN) + 127) // 128 * 128
+        pattern = NAN_BITS if nan_bands else SENTINEL_BITS
+        raw = torch.empty(2 * band + n, dtype=torch.float32, device=self.device)
+        bits = raw.view(torch.int32)
+        bits[:band].fill_(pattern)
+        bits[band + n:].fill_(pattern)
+        view = raw[band:band + n].view(*shape)
+        view.fill_(fill)
+        assert view.is_contiguous() and view.data_ptr() == raw.data_ptr() + 4 * band
+
+        def check(what=""):
+            for side, got in (("in front of", bits[:band]), ("behind", bits[band + n:])):
+                bad = (got != pattern).nonzero().flatten().cpu()
+                assert bad.numel() == 0, (f"{what}: {bad.numel()} floats of the guard band {side} the buffer {tuple(shape)} were "
+                                          f"overwritten, the first at band offset {int(bad[0])} of {band}")
+        return view, check
 
     def call(self, name, *args):
         """Tensors may be passed directly; they stay referenced for the duration of the call."""
