@@ -42,7 +42,10 @@ __device__ __forceinline__ Lerp hd_src(int dst, float scale, int n) {
     if (AC) {
         s = scale * (float)dst;
     } else {
-        s = scale * ((float)dst + 0.5f) - 0.5f;
+        // one rounding, as ATen's CPU kernel has it (its scale * (dst + 0.5) - 0.5 is contracted): the product alone rounds at
+        // the ulp of src + 0.5, and with D < Dc (scale 1.8: src 7.6 from 8.1) the lerp weight lost a bit -- 5.5 x the
+        // reference's own fp32 error in the disparity.  The device build contracts this anyway; a host build need not.
+        s = fmaf(scale, (float)dst + 0.5f, -0.5f);
         s = s < 0.f ? 0.f : s;
     }
     int i0 = (int)s;

@@ -82,6 +82,31 @@ class Backend:
         return self.lib.raw(name)
 
 
+class Guards:
+    """The banded buffers of one test: `out` for what a kernel writes, `inp` for what it reads; `check` after every call."""
+
+    def __init__(self, be):
+        self.be, self.checks = be, []
+
+    def out(self, *shape):
+        v, chk = self.be.banded(*shape, fill=float("nan"))
+        self.checks.append(chk)
+        return v
+
+    def inp(self, t):
+        if t is None:
+            return None
+        t = t.detach()
+        v, chk = self.be.banded(*t.shape, fill=0.0, nan_bands=True)
+        v.copy_(t)
+        self.checks.append(chk)
+        return v
+
+    def check(self, what):
+        for chk in self.checks:
+            chk(what)
+
+
 def ptr(t):
     """Identity marker for pointer arguments: Backend.call converts tensors to device pointers."""
     return t

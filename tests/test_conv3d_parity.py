@@ -19,10 +19,8 @@ the parity assertion (reads the buffer descriptors range-check to zero stay legi
 The shapes are the smallest ragged ones at which stx_conv3d_fwd's conv_plan / the weight-gradient dispatch pick each kernel; the
 comment of every row names the kernel and the epilogue it reaches.  Both backends through the C-ABI: host emulator and gfx950.
 """
-import atexit
 import contextlib
 import functools
-import json
 import os
 import re
 
@@ -30,122 +28,23 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.backends import Backend, be, ndhwc, ncdhw, tune  # noqa: F401
-from tests.parity import GRAD_FACTOR, VALUE_FACTOR, within
+from tests.backends import Backend, Guards, be, ndhwc, ncdhw, tune  # noqa: F401
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, PastTheFactor, RecordedDref, Verdict, listed_verdict, within
 
 NAN = float("nan")
 
 # d_ref of every tensor below, RECORDED from the fp32 CPU torch run on one thread (tests/golden/conv3d_parity_dref.json, keyed by the
-# parity-report name without the backend).  Recomputed on the spot it is not one number: the CPU convolution picks its blocking by
-# instruction set and thread count, and the same d_ref came out 0.42-3.4 x as large on another host (2 x between 4 and 16 threads
-# of one host: _one_thread) -- with a factor of 2 or 3 the verdict would follow the host CPU, not the kernel.  want64 is always
-# computed here.
-# The live value still guards the record: it must lie within DREF_DRIFT of the entry, a bound that judges the fixture, never a
-# kernel -- over twice the widest drift seen between hosts, while a slipped exponent, an entry of another tensor (values against
-# gradients, sums against outputs) or a table left over from other shapes is off by an order of magnitude.
+# parity-report name without the backend; why it is recorded and how the live value guards the record: tests/parity.py::RecordedDref).
 # STX_CONV3D_DREF_RECORD=<path> runs the module with the live values and writes them to <path> (a new or changed case).
-DREF_DRIFT = 8.0
 DREF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv3d_parity_dref.json")
-DREF_RECORD = os.environ.get("STX_CONV3D_DREF_RECORD")
-_recorded = {}
-if DREF_RECORD:
-    atexit.register(lambda: json.dump(_recorded, open(DREF_RECORD, "w"), indent=0, sort_keys=True))
-
-
-@functools.lru_cache(maxsize=None)
-def _dref_table():
-    with open(DREF_PATH) as f:
-        return json.load(f)
-
-
-def _dref(what, live):
-    key = re.sub(r"\[(emu|hip):", "[", what)
-    if DREF_RECORD:
-        assert _recorded.setdefault(key, live) == live, key
-        return live
-    rec = _dref_table()[key]
-    assert rec / DREF_DRIFT <= live <= rec * DREF_DRIFT, f"{key}: d_ref recorded {rec:.3e}, on this host {live:.3e}: a stale entry?"
-    return rec
-
-
-# ------------------------------------------------------------------------------------------ buffers
-class Guards:
-    """The banded buffers of one test: `out` for what a kernel writes, `inp` for what it reads; `check` after every call."""
-
-    def __init__(self, be):
-        self.be, self.checks = be, []
-
-    def out(self, *shape):
-        v, chk = self.be.banded(*shape, fill=NAN)
-        self.checks.append(chk)
-        return v
-
-    def inp(self, t):
-        if t is None:
-            return None
-        t = t.detach()
-        v, chk = self.be.banded(*t.shape, fill=0.0, nan_bands=True)
-        v.copy_(t)
-        self.checks.append(chk)
-        return v
-
-    def check(self, what):
-        for chk in self.checks:
-            chk(what)
-
-
-class PastTheFactor(AssertionError):
-    """Exactly the tensors SUMMATION_ORDER lists for the test are past the factor, each at its recorded ratio -- and nothing else:
-    a NaN, a touched guard band, any other tensor past the factor or a listed one elsewhere is a plain AssertionError."""
-
-
-TENSORS = ("sum", "sumsq", "dz", "dw")                # the suffix of `what` that names a tensor of a call; none: "out"
-RATIO_STEP = 0.005 * (1 + 1e-6)                       # the ratios of SUMMATION_ORDER are written to two decimals
-
-
-class Verdict:
-    """`within` for every tensor of a test; each goes to the parity report.  `listed` = {tensor: ratio}: the tensors of this test
-    the rule is known to refuse (SUMMATION_ORDER).  Every other tensor goes through `within` as it is, and a failure there fails
-    the test.  A listed tensor must be finite, must be refused by `within`, and must sit at its recorded ratio to the two decimals
-    written down (the kernels are deterministic, d_ref is recorded, gfx950 and the emulator agree to the bit): a kernel that
-    starts to pass has to leave the table, one that moves -- a lower-precision product path sits at 7-25 x -- fails the test."""
-
-    def __init__(self, log, listed, dref=_dref):
-        self.log, self.listed, self.seen, self.dref = log, listed, [], dref
-
-    def within(self, got, want64, dref, factor, what):
-        dref = self.dref(what, dref)
-        assert got.shape == want64.shape and dref > 0, (what, got.shape, want64.shape, dref)
-        bad = int((~torch.isfinite(got)).sum())
-        assert bad == 0, f"{what}: {bad} of {got.numel()} values are not finite (a read past a NaN band, or an unwritten value)"
-        tensor = what.rsplit(":", 1)[-1]
-        tensor = tensor if tensor in TENSORS else "out"
-        if tensor not in self.listed:
-            within(got, want64, dref, factor, what, self.log)
-            return
-        try:
-            within(got, want64, dref, factor, what, self.log)
-        except AssertionError as e:
-            ratio = e.args[0][1] / dref
-        else:
-            raise AssertionError(f"{what}: inside {factor} x d_ref now; take `{tensor}` out of SUMMATION_ORDER")
-        assert abs(ratio - self.listed[tensor]) <= RATIO_STEP, \
-            f"{what}: {ratio:.3f} x d_ref, SUMMATION_ORDER records {self.listed[tensor]:.2f} for the order of the additions alone"
-        self.seen.append(tensor)
-
-    def done(self):
-        assert sorted(self.seen) == sorted(self.listed), (self.seen, self.listed)
-        if self.listed:
-            raise PastTheFactor(", ".join(f"{t} {r:.2f}" for t, r in self.listed.items()))
+_dref = RecordedDref(DREF_PATH, "STX_CONV3D_DREF_RECORD")
 
 
 @pytest.fixture
 def verdict(request, parity_log):
+    """The tensors of a call are named by the suffix of `what`: sum, sumsq, dz, dw; none: "out" (tests/parity.py::Verdict)."""
     reason = SUMMATION_ORDER.get(re.sub(r"\[(emu|hip)-", "[", request.node.name))
-    if reason is None:
-        return Verdict(parity_log, {})
-    request.applymarker(pytest.mark.xfail(strict=True, raises=PastTheFactor, reason="summation order only, x d_ref: " + reason))
-    return Verdict(parity_log, {t: float(r) for t, r in (tr.split() for tr in reason.split(", "))})
+    return listed_verdict(request, parity_log, reason, "summation order only, x d_ref: ", dref=_dref)
 
 
 # Cases the rule refuses although nothing but the order of the fp32 additions separates the kernel from the reference: test name
