@@ -689,6 +689,30 @@ int stx_sequence_loss_fwd(const float* const* preds, const double* weights, int 
 int stx_sequence_loss_bwd(const float* gloss, const float* const* preds, const double* weights, int K, const float* gt, float maxdisp,
                           const int* count, float* const* gpreds, long long n, void* stream);
 
+/* ---- monster.hip: MonSter's mono / stereo mutual refinement (models/MonSter/monster.py:456-494, warp.py), NCHW fp32 -----------
+ * The sample of disp_warp: ix = (x - d) W / (W - 1) - 1/2, iy = y H / (H - 1) - 1/2 (formed in double), bilinear in both
+ * directions; zeros_pad == 0: padding 'border' (ix clipped to [0, W - 1], iy to [0, H - 1]; a clipped ix has no gradient to d),
+ * zeros_pad != 0: padding 'zeros'.  H, W >= 2, B C H W < 2^31, B <= 65535.  No float atomics, no memset, bitwise reproducible.
+ * stx_monster_flaw_fwd: out_a [B][C][H][W] = right sampled with disp_a [B][H][W], minus left (left NULL: the sample itself);
+ *   out_b the same with disp_b (both or neither); valid (NULL or [B][H][W]) = the validity map of disp_a: 1 under 'border', under
+ *   'zeros' 0 where the summed weight of the corners inside the image is below 0.9999, else 1.  One launch.
+ * stx_monster_flaw_bwd: from g_a / g_b (either may be NULL: no contribution), any of g_left = -(g_a + g_b), g_right (gathered:
+ *   every element written once, a's rows before b's, ascending output row, ascending output column; W <= 2048),
+ *   g_disp_a / g_disp_b [B][H][W] = -W / (W - 1) sum_c g d out / d ix (NULL = skipped).  At most two launches.
+ * stx_monster_scale_shift (monster.py:31-66): per image b of n elements, thr = the k-th smallest mono value (0-based, exact);
+ *   under mask (bytes; NULL: (gt > 0) & (mono > 1e-2) & (mono > thr)) the sums S_mm, S_m, N, S_mg, S_g in double and
+ *   out[b] = (scale, shift) = the solution of (X^T X + 1e-6 I) p = X^T y in double, rounded once; an empty mask gives (0, 0).
+ *   stats [B][8] doubles: the five sums, thr, k, 0.  1 <= n < 2^24, 0 <= k < n.  One workgroup per image, no host sync.
+ * stx_monster_apply_scale_shift: out[b] = scale_b x[b] + shift_b (with_shift == 0: scale_b x[b], the backward). */
+int stx_monster_flaw_fwd(const float* left, const float* right, const float* disp_a, const float* disp_b, int zeros_pad, float* out_a,
+                         float* out_b, float* valid, int B, int C, int H, int W, void* stream);
+int stx_monster_flaw_bwd(const float* g_a, const float* g_b, const float* right, const float* disp_a, const float* disp_b, int zeros_pad,
+                         float* g_left, float* g_right, float* g_disp_a, float* g_disp_b, int B, int C, int H, int W, void* stream);
+int stx_monster_scale_shift(const float* mono, const float* gt, const unsigned char* mask, long long k, float* out, void* stats, int B,
+                            long long n, void* stream);
+int stx_monster_apply_scale_shift(const float* x, const float* scale_shift, int with_shift, float* out, int B, long long n,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,11 @@ SIGNATURES = {
     "stx_sequence_loss_workspace_floats": [_L],
     "stx_sequence_loss_fwd": [_P, _P, _I, _P, _F, _P, _P, _P, _L, _P],
     "stx_sequence_loss_bwd": [_P, _P, _P, _I, _P, _F, _P, _P, _L, _P],
+    # monster.hip
+    "stx_monster_flaw_fwd": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_monster_flaw_bwd": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_monster_scale_shift": [_P, _P, _P, _L, _P, _P, _I, _L, _P],
+    "stx_monster_apply_scale_shift": [_P, _P, _I, _P, _I, _L, _P],
     # bn.hip
     "stx_bn_reduce_blocks": [],
     "stx_bn_stats_rows": [_L, _I],

@@ -12,6 +12,7 @@ from . import RAFTStereo  # noqa: F401  (correlation blocks only)
 from . import DEFOMStereo  # noqa: F401  (correlation block only)
 from . import StereoAnywhere  # noqa: F401  (volume-in correlation block and volume estimators only)
 from . import STTR  # noqa: F401  (transformer and regression head)
+from . import MonSter  # noqa: F401  (mono / stereo mutual refinement: scale-shift fit and feature flaws)
 
 
 def load_checkpoint_flexible(model, checkpoint_path, state_dict_key=None):

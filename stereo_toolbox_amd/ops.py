@@ -3580,3 +3580,209 @@ def disp_attention_masks(seed, p, N, L, C, F, layers):
     out = torch.empty(layers, DISP_ATTN_SITES, N, L, max(C, F), dtype=torch.uint8, device=seed.device)
     _call("stx_disp_attention_masks", _p(seed.contiguous()), p, _p(out), N, L, C, F, layers)
     return out
+
+
+# --------------------------------------------------------------------------------------- MonSter mutual refinement
+MONSTER_PADDING = ("border", "zeros")                                    # warp.py:58
+MONSTER_MAX_N = 1 << 24                                                  # csrc/monster.hip: counts of the radix select
+MONSTER_BWD_MAX_W = 2048                                                 # csrc/monster.hip MS_MAX_W (gradient to the sampled map)
+
+
+def _low_dtype(t):
+    return t.dtype if isinstance(t, torch.Tensor) and t.dtype in _LOW else None
+
+
+def _as_dtype(out, dtype):
+    if dtype is None:
+        return out
+    return tuple(t.to(dtype) for t in out) if isinstance(out, tuple) else out.to(dtype)
+
+
+def _monster_pair(who, img, disps, padding_mode, left=None):
+    """The shape rules of the warp, checked on the shapes alone before anything is copied or launched."""
+    if padding_mode not in MONSTER_PADDING:
+        raise StxError(f"{who}: padding_mode {padding_mode!r} is not one of {MONSTER_PADDING}")
+    if not isinstance(img, torch.Tensor) or img.dim() != 4:
+        raise StxError(f"{who}: the sampled map must be [B, C, H, W], got {tuple(getattr(img, 'shape', ()))}")
+    B, C, H, W = img.shape
+    if left is not None and (not isinstance(left, torch.Tensor) or left.shape != img.shape):
+        raise StxError(f"{who}: left {tuple(getattr(left, 'shape', ()))} does not match right {tuple(img.shape)}")
+    for name, d in disps:
+        if not isinstance(d, torch.Tensor) or tuple(d.shape) != (B, 1, H, W):
+            raise StxError(f"{who}: {name} must be [B, 1, H, W] = {(B, 1, H, W)}, got {tuple(getattr(d, 'shape', ()))}")
+    if H < 2 or W < 2:
+        raise StxError(f"{who}: the reference's sampling grid divides by H - 1 and W - 1: H, W >= 2 needed, got {H} x {W}")
+    out = []
+    for name, t in (("left", left), ("right", img), *disps):
+        if t is not None:
+            t = t.contiguous()
+            _chk(t, name, 4)
+        out.append(t)
+    return out
+
+
+class MonsterFlawFn(torch.autograd.Function):
+    """disp_warp(right, d)[0] - left (monster.py:469-473, refinement.py:403-407) for one or two disparities on
+    stx_monster_flaw_fwd / _bwd: one forward launch; the backward is a per-pixel kernel and a gather, without float atomics.
+    Saves the inputs only (right and the disparities; left is not needed).  left None: the warped map itself."""
+
+    @staticmethod
+    def forward(ctx, left, right, da, db, zeros, want_valid):
+        B, C, H, W = right.shape
+        oa = torch.empty_like(right)
+        ob = torch.empty_like(right) if db is not None else None
+        valid = torch.empty(B, 1, H, W, dtype=torch.float32, device=right.device) if want_valid else None
+        _call("stx_monster_flaw_fwd", _p(left), _p(right), _p(da), _p(db), zeros, _p(oa), _p(ob), _p(valid), B, C, H, W)
+        if not isinstance(ctx, _NoCtx):
+            ctx.set_materialize_grads(False)
+        ctx.save_for_backward(right, da, db)
+        ctx.zeros = zeros
+        if valid is not None:
+            ctx.mark_non_differentiable(valid)
+        return oa, ob, valid
+
+    @staticmethod
+    def backward(ctx, ga, gb, _gvalid):
+        right, da, db = ctx.saved_tensors
+        if ga is None and gb is None:
+            return None, None, None, None, None, None
+        B, C, H, W = right.shape
+        ga, gb = (None if g is None else g.contiguous() for g in (ga, gb))
+        need = ctx.needs_input_grad
+        if need[1] and W > MONSTER_BWD_MAX_W:
+            raise StxError(f"monster_flaws: W={W} above the {MONSTER_BWD_MAX_W} the gradient to the sampled map supports")
+        g_left = torch.empty_like(right) if need[0] else None
+        g_right = torch.empty_like(right) if need[1] else None
+        g_da = torch.empty_like(da) if need[2] else None
+        g_db = torch.empty_like(db) if db is not None and need[3] else None
+        if g_left is None and g_right is None and g_da is None and g_db is None:
+            return None, None, None, None, None, None
+        _call("stx_monster_flaw_bwd", _p(ga), _p(gb), _p(right), _p(da), _p(db), ctx.zeros, _p(g_left), _p(g_right), _p(g_da),
+              _p(g_db), B, C, H, W)
+        return g_left, g_right, g_da, g_db, None, None
+
+
+def _monster_flaw_call(left, right, da, db, padding_mode, want_valid):
+    zeros = int(padding_mode == "zeros")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (left, right, da, db)):
+        return MonsterFlawFn.apply(left, right, da, db, zeros, want_valid)
+    return MonsterFlawFn.forward(_NoCtx(), left, right, da, db, zeros, want_valid)
+
+
+@fp32_region
+def _monster_flaws(left, right, disp_a, disp_b, padding_mode):
+    who = "monster_flaws"
+    disps = (("disp_a", disp_a),) + ((("disp_b", disp_b),) if disp_b is not None else ())
+    if not isinstance(left, torch.Tensor):
+        raise StxError(f"{who}: left must be a [B, C, H, W] tensor, got {type(left).__name__}")
+    left, right, da, *rest = _monster_pair(who, right, disps, padding_mode, left=left)
+    fa, fb, _ = _monster_flaw_call(left, right, da, rest[0] if rest else None, padding_mode, False)
+    return fa if disp_b is None else (fa, fb)
+
+
+def monster_flaws(left, right, disp_a, disp_b=None, padding_mode="border"):
+    """left, right [B, C, H, W], disp_a (and disp_b) [B, 1, H, W] -> flaw_a (, flaw_b) = disp_warp(right, d)[0] - left of the
+    reference's MonSter (monster.py:469-473): right sampled at ix = (x - d) W / (W - 1) - 1/2, iy = y H / (H - 1) - 1/2, bilinear
+    in both directions, padding 'border' (the model's) or 'zeros'.  Both flaws come from one launch and one autograd node,
+    differentiable in left, right and the disparities; the backward is bitwise reproducible (no float atomics).  fp16 / bf16
+    maps are cast up and the flaws returned in the dtype of `right`, as the reference's `interp` does."""
+    low = _low_dtype(right)
+    return _as_dtype(_monster_flaws(*_to_fp32((left, right, disp_a, disp_b)), padding_mode), low)
+
+
+@fp32_region
+def _monster_disp_warp(img, disp, padding_mode):
+    _, img, disp = _monster_pair("monster_disp_warp", img, (("disp", disp),), padding_mode)
+    warped, _, valid = _monster_flaw_call(None, img, disp, None, padding_mode, True)
+    return warped, valid
+
+
+def monster_disp_warp(img, disp, padding_mode="border"):
+    """img [B, C, H, W], disp [B, 1, H, W] -> (warped, valid_mask), both [B, C, H, W] (the mask a broadcast view, no gradient):
+    the reference's disp_warp (MonSter/warp.py:53-79).  valid_mask is formed from the weights of the corners inside the image:
+    1 everywhere under 'border'; under 'zeros' 0 where their sum is below 0.9999, else 1."""
+    low = _low_dtype(img)
+    warped, valid = _as_dtype(_monster_disp_warp(*_to_fp32((img, disp)), padding_mode), low)
+    return warped, valid.expand_as(warped)
+
+
+def _monster_fit_args(who, mono, gt, mask):
+    for name, t in (("mono", mono), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or t.dim() < 2:
+            raise StxError(f"{who}: {name} must be a [B, ...] tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if gt.shape != mono.shape:
+        raise StxError(f"{who}: gt {tuple(gt.shape)} does not match mono {tuple(mono.shape)}")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != mono.shape):
+        raise StxError(f"{who}: mask must be a bool tensor of mono's shape {tuple(mono.shape)}")
+    B = mono.shape[0]
+    n = mono.numel() // max(1, B)
+    if B < 1 or not 0 < n < MONSTER_MAX_N:
+        raise StxError(f"{who}: {n} elements per image outside 1..2^24 - 1")
+    mono, gt = mono.detach().contiguous(), gt.detach().contiguous()
+    _chk(mono, "mono")
+    _chk(gt, "gt")
+    if mask is not None:
+        if not on_device(mask):
+            raise StxError(f"{who}: mask: expected a ROCm device tensor, got {mask.device}")
+        mask = mask.contiguous().view(torch.uint8)
+    return mono, gt, mask, B, n
+
+
+@fp32_region
+def _monster_fit(mono, gt, mask, who="monster_scale_shift"):
+    mono, gt, mask, B, n = _monster_fit_args(who, mono, gt, mask)
+    ss = torch.empty(B, 2, dtype=torch.float32, device=mono.device)
+    stats = torch.empty(B, 8, dtype=torch.float64, device=mono.device)
+    k = int(0.2 * n)                                                     # monster.py:47, the same Python expression
+    _call("stx_monster_scale_shift", _p(mono), _p(gt), _p(mask), k, _p(ss), _p(stats), B, n)
+    return ss, stats
+
+
+def monster_scale_shift(mono, gt, mask=None):
+    """mono, gt [B, 1, H, W] -> [B, 2] fp32 on the device, per image (scale, shift) of compute_scale_shift (monster.py:31-66): the
+    least-squares fit gt ~ scale mono + shift, ridge 1e-6, over mask, by default (gt > 0) & (mono > 1e-2) & (mono > the value of
+    rank int(0.2 n) of mono).  An empty mask gives (0, 0).  Constants of the graph; no host synchronisation."""
+    return _monster_fit(*_to_fp32((mono, gt)), mask)[0]
+
+
+def monster_fit_stats(mono, gt, mask=None):
+    """What `monster_scale_shift` summed, [B, 8] fp64: S_mm, S_m, N, S_mg, S_g, the rank threshold, the rank, 0."""
+    return _monster_fit(*_to_fp32((mono, gt)), mask)[1]
+
+
+class MonsterApplyFn(torch.autograd.Function):
+    """scale_b * mono[b] + shift_b on stx_monster_apply_scale_shift; the gradient goes to mono only (scale and shift are
+    constants, as the reference's `.item()` makes them)."""
+
+    @staticmethod
+    def forward(ctx, mono, ss):
+        B = mono.shape[0]
+        out = torch.empty_like(mono)
+        _call("stx_monster_apply_scale_shift", _p(mono), _p(ss), 1, _p(out), B, mono.numel() // B)
+        ctx.save_for_backward(ss)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ss, = ctx.saved_tensors
+        g = g.contiguous()
+        gm = torch.empty_like(g)
+        _call("stx_monster_apply_scale_shift", _p(g), _p(ss), 0, _p(gm), g.shape[0], g.numel() // g.shape[0])
+        return gm, None
+
+
+@fp32_region
+def _monster_align(mono, gt, mask):
+    ss, _ = _monster_fit(mono, gt, mask, who="monster_align")
+    mono = mono.contiguous()
+    _chk(mono, "mono")
+    if torch.is_grad_enabled() and mono.requires_grad:
+        return MonsterApplyFn.apply(mono, ss)
+    return MonsterApplyFn.forward(_NoCtx(), mono, ss)
+
+
+def monster_align(mono, gt, mask=None):
+    """mono, gt [B, 1, H, W] -> scale_b * mono[b] + shift_b with `monster_scale_shift`'s fit per image (monster.py:463-467, batched:
+    no Python loop, no host synchronisation).  Differentiable in mono with the fit held constant; returned in mono's dtype."""
+    low = _low_dtype(mono)
+    return _as_dtype(_monster_align(*_to_fp32((mono, gt)), mask), low)
