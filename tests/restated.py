@@ -2,6 +2,8 @@
 of IGEV's geometry lookup (reference models/IGEVStereo/geometry.py:7-70) and convex upsampling (submodule.py:243-255), and
 StereoAnywhere's truncation mask (utils/utils.py:216-238).  A restatement used by a single test module lives in that module.
 """
+import math
+
 import torch
 
 
@@ -55,6 +57,40 @@ def upsample(disp_low, wts):
         tap = p[:, t // 3:t // 3 + h, t % 3:t % 3 + w]
         out = out + wts[:, t] * tap.repeat_interleave(4, 1).repeat_interleave(4, 2)
     return out
+
+
+def corr1d_pyramid(f1, f2, levels):
+    """f1 [B,C,H,W1], f2 [B,C,H,W2] -> [[B,H,W1,W2_i]]: einsum / sqrt(C), then pairwise averages along the last axis
+    (reference models/RAFTStereo/corr.py:31-156)."""
+    cp = [torch.einsum("aijk,aijh->ajkh", f1, f2) / torch.sqrt(torch.tensor(float(f1.shape[1]), dtype=f1.dtype))]
+    for _ in range(levels - 1):
+        cp.append(pool(cp[-1]))
+    return cp
+
+
+def convex(flow, mask, f, scale):
+    """out[n, d, f y + j, f x + i] = sum_t softmax_t(mask[n, (t f + j) f + i, y, x]) * scale * flow[n, d, y + t/3 - 1, x + t%3 - 1]"""
+    N, D, H, W = flow.shape
+    s = torch.softmax(mask.view(N, 9, f, f, H, W), dim=1)
+    p = torch.nn.functional.pad(scale * flow, (1, 1, 1, 1))
+    out = 0
+    for t in range(9):
+        tap = p[:, :, t // 3:t // 3 + H, t % 3:t % 3 + W]
+        out = out + s[:, t].unsqueeze(1) * tap.view(N, D, 1, 1, H, W)
+    return out.permute(0, 1, 4, 2, 5, 3).reshape(N, D, f * H, f * W)
+
+
+def estimates(volume):
+    """[B,1,H,W1,W2] -> (disp_l, conf_l, disp_r, conf_r), StereoAnywhere utils/utils.py:112-170 without the repeats and meshgrids"""
+    v = volume.squeeze(1)
+    W1, W2 = v.shape[2:]
+    a1, a2 = torch.arange(W1, dtype=v.dtype), torch.arange(W2, dtype=v.dtype)
+    pl, pr = torch.softmax(v, dim=3), torch.softmax(v, dim=2)
+    disp_l = a1.view(1, 1, W1) - torch.sum(pl * a2, 3)
+    disp_r = torch.sum(pr * a1.view(1, 1, W1, 1), 2) - a2
+    conf_l = 1 - (-torch.sum(pl * torch.log2(pl + 1e-6), dim=3) / math.log2(W2))
+    conf_r = 1 - (-torch.sum(pr * torch.log2(pr + 1e-6), dim=2) / math.log2(W1))
+    return tuple(t.unsqueeze(1) for t in (disp_l, conf_l, disp_r, conf_r))
 
 
 def _pack(levels_list):

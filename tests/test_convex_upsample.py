@@ -24,7 +24,7 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.convex_upsample_config import (CASES, LOSS_GAMMA, LOSS_KS, LOSS_MAXDISP, LOSS_PREDICTIONS, LOSS_SHAPE, PIXEL_CASES,
                                                  PIXEL_SCALE, inputs, loss_inputs, pixel_inputs, trainer_weights)
 from tests.parity import GRAD_FACTOR, VALUE_FACTOR, env, pin, sync, within, within_fixture  # noqa: F401
-from tests.restated import upsample
+from tests.restated import convex, upsample
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -39,18 +39,6 @@ def gold():
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
-def convex(flow, mask, f, scale):
-    """out[n, d, f y + j, f x + i] = sum_t softmax_t(mask[n, (t f + j) f + i, y, x]) * scale * flow[n, d, y + t/3 - 1, x + t%3 - 1]"""
-    N, D, H, W = flow.shape
-    s = torch.softmax(mask.view(N, 9, f, f, H, W), dim=1)
-    p = torch.nn.functional.pad(scale * flow, (1, 1, 1, 1))
-    out = 0
-    for t in range(9):
-        tap = p[:, :, t // 3:t // 3 + H, t % 3:t % 3 + W]
-        out = out + s[:, t].unsqueeze(1) * tap.view(N, D, 1, 1, H, W)
-    return out.permute(0, 1, 4, 2, 5, 3).reshape(N, D, f * H, f * W)
-
-
 def trainer_loss(init_disp, disp_preds, gt, maxdisp, loss_gamma=LOSS_GAMMA):
     """trainer/trainer_torchrun.py:272-284 (the test of losses.sequence_loss compares with the fixture of the trainer's own run)"""
     mask = (gt > 0) * (gt < maxdisp - 1)

@@ -30,7 +30,7 @@ from tests.golden.corr1d_config import (ALL_CASES, CASES, DEFOM_SCALE_RADIUS, DE
                                         SHAPE_CASES, SUBSAMPLE, columns, inputs, iter_inputs, out_channels, subsample)
 from tests.parity import (EPS, GRAD_FACTOR, VALUE_FACTOR, Env, env, near, on, pin_fixture, pin_subsample, sync, within,  # noqa: F401
                           within_fixture)
-from tests.restated import _pack, pool, sample
+from tests.restated import _pack, corr1d_pyramid as pyramid, pool, sample
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "corr1d.npz")
 ITER = f"iter{ITER_CALLS}"
@@ -42,14 +42,6 @@ def gold():
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
-def pyramid(f1, f2, levels):
-    """f1 [B,C,H,W1], f2 [B,C,H,W2] -> [[B,H,W1,W2_i]]: einsum / sqrt(C), then pairwise averages along the last axis."""
-    cp = [torch.einsum("aijk,aijh->ajkh", f1, f2) / torch.sqrt(torch.tensor(float(f1.shape[1]), dtype=f1.dtype))]
-    for _ in range(levels - 1):
-        cp.append(pool(cp[-1]))
-    return cp
-
-
 def raft_lookup(cp, coords, radius):
     B, _, H, W = coords.shape
     dx = torch.arange(-radius, radius + 1, dtype=coords.dtype)

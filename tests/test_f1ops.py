@@ -9,16 +9,12 @@ import pytest
 import torch
 
 from oracle import torch_oracle as O
-from tests.backends import BACKENDS, Backend  # noqa: F401
+from tests.backends import be  # noqa: F401
 from tests.golden.f1ops_config import CORR_CASES, VAR_CASES, WARP_CASES, corr_inputs, var_inputs, warp_inputs
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, within
 from stereo_toolbox_amd.utils import synthetic_tensor
 
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f1ops.npz"))
-
-
-@pytest.fixture(params=BACKENDS)
-def be(request):
-    return Backend(request.param)
 
 
 def _g(name):
@@ -28,6 +24,21 @@ def _g(name):
 def _close(a, b, tol, what):
     err = (a.cpu() - b).abs().max().item()
     assert err <= tol * max(1.0, b.abs().max().item()), (what, err)
+
+
+def _fp64(fn, ts, g):
+    """The oracle in fp64 from the fp32 inputs cast up: (value, [gradient of <value, g> w.r.t. every input])."""
+    a = [t.double().clone().requires_grad_() for t in ts]
+    y = fn(*a)
+    y.backward(g.double())
+    return y.detach(), [t.grad for t in a]
+
+
+def _rule(got, name, want64, factor):
+    """The fp64 parity rule (tests/parity.py::within) where a flat bound was wider than it: the kernel within `factor` x d_ref
+    of the oracle in fp64, d_ref = the distance of the REFERENCE's own fp32 result (the fixture) from it.  The same inputs run
+    under the recorded d_ref of tests/test_iterative_kernels_parity.py; the ratios measured there are 2.6 at most."""
+    within(got, want64, (_g(name).double() - want64).abs().max().item(), factor, name)
 
 
 def test_oracle_matches_reference_fixtures():
@@ -63,8 +74,8 @@ def test_warp_fwd_bwd(be, case):
     # the validity mask is a discontinuity: exactly the reference's pixels are zeroed
     assert torch.equal(out.cpu() == 0, _g(f"warp_{name}") == 0)
     be.call("stx_warp_bwd", be.dev(g), be.dev(x), be.dev(d), gx, gd, B, C, H, W)
-    _close(gx, _g(f"warp_{name}_gx"), 2e-6, "gx")
-    _close(gd, _g(f"warp_{name}_gd"), 1e-5, "gdisp")
+    _close(gx, _g(f"warp_{name}_gx"), 2e-6, "gx")            # (2e-6 of the maximum is below 3 x d_ref here, and on the output)
+    _rule(gd, f"warp_{name}_gd", _fp64(O.pcw_warp, (x, d), g)[1][1], GRAD_FACTOR)
     # either gradient alone
     gx2, gd2 = be.empty(B, C, H, W), be.empty(B, 1, H, W)
     be.call("stx_warp_bwd", be.dev(g), be.dev(x), be.dev(d), gx2, None, B, C, H, W)
@@ -105,12 +116,13 @@ def test_corr_volume_fwd_bwd(be, case):
     vol = be.empty(B, G, 2 * md + 1, H, W)
     be.call("stx_corr_volume_fwd", be.dev(a), be.dev(b), vol, B, C, H, W, md, G)
     ref = _g(f"corr_{name}")
-    _close(vol, ref, 2e-6, "corr")
+    v64, (ga64, gb64) = _fp64(lambda a, b: O.pcw_correlation_volume(a, b, md, G), (a, b), g)
+    _rule(vol, f"corr_{name}", v64, VALUE_FACTOR)
     assert torch.equal(vol.cpu() == 0, ref == 0)          # the zero regions (w < i, columns >= |i| of the negative slices) exactly
     ga, gb = be.empty(B, C, H, W), be.empty(B, C, H, W)
     be.call("stx_corr_volume_bwd", be.dev(g), be.dev(a), be.dev(b), ga, gb, B, C, H, W, md, G)
-    _close(ga, _g(f"corr_{name}_ga"), 3e-6, "gref")
-    _close(gb, _g(f"corr_{name}_gb"), 3e-6, "gtgt")
+    _rule(ga, f"corr_{name}_ga", ga64, GRAD_FACTOR)
+    _rule(gb, f"corr_{name}_gb", gb64, GRAD_FACTOR)
     ga2, gb2 = be.empty(B, C, H, W), be.empty(B, C, H, W)
     be.call("stx_corr_volume_bwd", be.dev(g), be.dev(a), be.dev(b), ga2, None, B, C, H, W, md, G)
     be.call("stx_corr_volume_bwd", be.dev(g), be.dev(a), be.dev(b), None, gb2, B, C, H, W, md, G)
@@ -151,19 +163,21 @@ def test_disparity_variance_fwd_bwd(be, case):
     name, B, D, H, W = VAR_CASES[case]
     x, d, s, g = var_inputs(B, D, H, W, 300 + 10 * case)
     out = be.empty(B, 1, H, W)
+    v64, (vx64, vd64) = _fp64(lambda x, d: O.cf_disparity_variance(x, D, d), (x, d), g)
+    c64, (cx64, cd64, cs64) = _fp64(lambda x, d, s: O.cf_disparity_variance_confidence(x, s, d), (x, d, s), g)
     be.call("stx_disparity_variance_fwd", be.dev(x), be.dev(d), None, out, B, D, H * W)
-    _close(out, _g(f"var_{name}"), 1e-6, "variance")
+    _rule(out, f"var_{name}", v64, VALUE_FACTOR)
     gx, gd = be.empty(B, D, H, W), be.empty(B, 1, H, W)
     be.call("stx_disparity_variance_bwd", be.dev(g), be.dev(x), be.dev(d), None, gx, gd, None, B, D, H * W)
-    _close(gx, _g(f"var_{name}_gx"), 1e-6, "gx")
-    _close(gd, _g(f"var_{name}_gd"), 2e-6, "gdisp")
+    _rule(gx, f"var_{name}_gx", vx64, GRAD_FACTOR)
+    _rule(gd, f"var_{name}_gd", vd64, GRAD_FACTOR)
     be.call("stx_disparity_variance_fwd", be.dev(x), be.dev(d), be.dev(s), out, B, D, H * W)
-    _close(out, _g(f"conf_{name}"), 1e-6, "confidence")
+    _rule(out, f"conf_{name}", c64, VALUE_FACTOR)
     gs = be.empty(B, D, H, W)
     be.call("stx_disparity_variance_bwd", be.dev(g), be.dev(x), be.dev(d), be.dev(s), gx, gd, gs, B, D, H * W)
-    _close(gx, _g(f"conf_{name}_gx"), 1e-6, "gx")
-    _close(gd, _g(f"conf_{name}_gd"), 2e-6, "gdisp")
-    _close(gs, _g(f"conf_{name}_gs"), 2e-6, "gsamples")
+    _rule(gx, f"conf_{name}_gx", cx64, GRAD_FACTOR)
+    _rule(gd, f"conf_{name}_gd", cd64, GRAD_FACTOR)
+    _rule(gs, f"conf_{name}_gs", cs64, GRAD_FACTOR)
 
 
 @pytest.mark.parametrize("envname", ["emu", pytest.param("hip", marks=pytest.mark.gpu)])

@@ -25,7 +25,7 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.stereoanywhere_config import (ATTENUATION, BLOCK_CASES, EST_CASES, EST_GPU_ONLY, EST_WHOLE, MASK_THRESHOLDS, OUTPUTS,
                                                 SUBSAMPLE, block_inputs, block_out_width, est_inputs, mask_inputs, subsample)
 from tests.parity import EPS, GRAD_FACTOR, VALUE_FACTOR, Env, env, near, on, pin_fixture, pin_subsample, sync, within, within_fixture  # noqa: F401
-from tests.restated import _pack, pool, sample, truncation_mask
+from tests.restated import _pack, estimates, pool, sample, truncation_mask
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stereoanywhere.npz")
 
@@ -36,19 +36,6 @@ def gold():
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
-def estimates(volume):
-    """[B,1,H,W1,W2] -> (disp_l, conf_l, disp_r, conf_r), utils/utils.py:112-170 without the repeats and meshgrids"""
-    v = volume.squeeze(1)
-    W1, W2 = v.shape[2:]
-    a1, a2 = torch.arange(W1, dtype=v.dtype), torch.arange(W2, dtype=v.dtype)
-    pl, pr = torch.softmax(v, dim=3), torch.softmax(v, dim=2)
-    disp_l = a1.view(1, 1, W1) - torch.sum(pl * a2, 3)
-    disp_r = torch.sum(pr * a1.view(1, 1, W1, 1), 2) - a2
-    conf_l = 1 - (-torch.sum(pl * torch.log2(pl + 1e-6), dim=3) / math.log2(W2))
-    conf_r = 1 - (-torch.sum(pr * torch.log2(pr + 1e-6), dim=2) / math.log2(W1))
-    return tuple(t.unsqueeze(1) for t in (disp_l, conf_l, disp_r, conf_r))
-
-
 def block_pyramid(vol, maps, L):
     v = vol.squeeze(3)
     if maps is not None:
