@@ -84,6 +84,18 @@ def within(got, want64, dref, factor, what, log=None):
     assert err <= tol, (what, err, dref)
 
 
+def within_inf(got, want64, dref, factor, what, log=None, rule=None):
+    """`within` over the finite entries; the -inf entries of want64 compared by equality.  `rule`: another form of the rule with
+    the arguments (got, want64, dref, factor, what), such as Verdict.within."""
+    inf = torch.isinf(want64)
+    assert torch.equal(got.detach().cpu() == float("-inf"), inf), what
+    got, want64 = got.detach().cpu().masked_fill(inf, 0.0), want64.masked_fill(inf, 0.0)
+    if rule is None:
+        within(got, want64, dref, factor, what, log)
+    else:
+        rule(got, want64, dref, factor, what)
+
+
 def within_fixture(got, gold, key, factor, what, log=None):
     """`within` against the tensor a fixture stores as `key:f64` / `key:dref`."""
     within(got, torch.from_numpy(gold[key + ":f64"]), float(gold[key + ":dref"]), factor, what, log)

@@ -1,10 +1,14 @@
 """Plain-torch restatements of reference code that more than one test module compares with: the gather form (no grid_sample)
 of IGEV's geometry lookup (reference models/IGEVStereo/geometry.py:7-70) and convex upsampling (submodule.py:243-255), and
-StereoAnywhere's truncation mask (utils/utils.py:216-238).  A restatement used by a single test module lives in that module.
+StereoAnywhere's truncation mask (utils/utils.py:216-238), STTR's attention with relative positions (models/STTR/attention.py) and its
+matching head (models/STTR/regression_head.py).  A restatement used by a single test module lives in that module.
 """
 import math
 
 import torch
+import torch.nn.functional as F
+
+from tests.golden.sttr_config import SCALE as STTR_SCALE
 
 
 def pool(x):
@@ -105,3 +109,107 @@ def truncation_mask(disp, conf, conf_th, atten):
     c = (conf if conf_th is None else (conf > conf_th).to(disp.dtype)).unsqueeze(4)
     x = (a.view(1, 1, 1, W) - disp).unsqueeze(4) - a.view(1, 1, 1, 1, W)
     return 1 * (1 - c) + c * (torch.sigmoid(x) * (1 - atten) + atten)
+
+
+# ------------------------------------------------------------------------------------------ STTR: attention
+NINF = float("-inf")
+
+
+def relative_index(W, device=None):
+    """[W * W]: the row (W - 1 - w) + v of the [2W-1] positional table that the pair (query w, key v) reads"""
+    return (torch.arange(W - 1, -1, -1, device=device).view(W, 1) + torch.arange(W, device=device).view(1, W)).view(-1)
+
+
+def attention_core(q, k, v, q_r, k_r, causal):
+    """STTR's attention between the projections (reference models/STTR/attention.py): q (scaled), k, v [W, B, E, hd]; q_r, k_r
+    [W, W, E, hd] the projected positional rows of every pair, or both None -> (o [W, B, E, hd], softmax [B, E, W, W], the scores
+    [B, E, W, W] with -inf above the diagonal when causal)."""
+    W, B, E, hd = q.shape
+    attn = torch.einsum("wnec,vnec->newv", q, k)
+    if q_r is not None:
+        attn = attn + torch.einsum("wnec,wvec->newv", q, k_r) + torch.einsum("vnec,wvec->newv", k, q_r)
+    if causal:
+        attn = attn + torch.triu(torch.full((W, W), NINF, dtype=attn.dtype, device=attn.device), 1)
+    raw = attn
+    attn = F.softmax(attn, dim=-1)
+    v_o = torch.bmm(attn.view(B * E, W, W), v.permute(1, 2, 0, 3).reshape(B * E, W, hd))
+    return v_o.reshape(B, E, W, hd).permute(2, 0, 1, 3), attn, raw
+
+
+def attention(form, P, prefix, query, key, causal, pos, E):
+    """One MultiheadAttentionRelative call with key = value -> (v_o, attn, raw_attn).  P: parameters by name."""
+    W, B, C = query.shape
+    hd = C // E
+    w_in, b_in = P[prefix + "in_proj_weight"], P[prefix + "in_proj_bias"]
+    if query is key:
+        q, k, v = F.linear(query, w_in, b_in).chunk(3, dim=-1)
+    else:
+        q = F.linear(query, w_in[:C], b_in[:C])
+        k, v = F.linear(key, w_in[C:], b_in[C:]).chunk(2, dim=-1)
+    scaling = float(hd) ** -0.5
+    q = (q * scaling).contiguous().view(W, B, E, hd)
+    k, v = k.contiguous().view(W, B, E, hd), v.contiguous().view(W, B, E, hd)
+    q_r = k_r = None
+    if pos is not None:
+        idx = relative_index(W, query.device)
+        if form == "stock":
+            q_r, k_r = F.linear(torch.index_select(pos, 0, idx).view(W, W, -1), w_in[:2 * C], b_in[:2 * C]).chunk(2, dim=-1)
+            q_r, k_r = (q_r * scaling).contiguous().view(W, W, E, hd), k_r.contiguous().view(W, W, E, hd)
+        else:
+            q_r = (F.linear(pos, w_in[:C], b_in[:C]) * scaling)[idx].view(W, W, E, hd)
+            k_r = F.linear(pos, w_in[C:2 * C], b_in[C:2 * C])[idx].view(W, W, E, hd)
+    v_o, attn, raw = attention_core(q, k, v, q_r, k_r, causal)
+    v_o = F.linear(v_o.reshape(W, B, C), P[prefix + "out_proj.weight"], P[prefix + "out_proj.bias"])
+    return v_o, attn.sum(dim=1) / E, raw.sum(dim=1)
+
+
+# ------------------------------------------------------------------------------------------ STTR: matching head
+def constants(W):
+    """log mu = log nu and log 2W: fp32 host tensors, in an fp64 run as well"""
+    return (torch.cat([torch.ones(W), torch.tensor([W]).float()]) / (2 * W)).log(), torch.log(torch.tensor([2.0 * W]))
+
+
+def transported(attn, phi, ot, iters):
+    """[N, H, W, W] -> P [N, H, W+1, W+1]"""
+    N, H, W, _ = attn.shape
+    S = torch.cat([torch.cat([attn, phi.expand(N, H, W, 1)], -1), phi.expand(N, H, 1, W + 1)], -2)
+    if not ot:
+        return torch.softmax(S, dim=-1)
+    lm, l2w = constants(W)
+    u = torch.zeros(N, H, W + 1, dtype=attn.dtype)
+    for _ in range(iters):
+        v = lm - torch.logsumexp(S + u.unsqueeze(3), dim=2)
+        u = lm - torch.logsumexp(S + v.unsqueeze(2), dim=3)
+    return (S + u.unsqueeze(3) + v.unsqueeze(2) + l2w).exp()
+
+
+def target_of(disp_gt):
+    """full-resolution ground truth [N, 3H, 3W] -> the right position of every sampled pixel in low-resolution columns"""
+    w = disp_gt.shape[-1]
+    return (torch.arange(w, dtype=torch.float32) - disp_gt)[..., 1::STTR_SCALE, 1::STTR_SCALE] / float(STTR_SCALE)
+
+
+def regress(P, mask, target):
+    """P [N, H, W+1, W+1] -> the five outputs ('gt' only with a target) and 'norm', the arg-max and where norm was forced.  The steps come in
+    the order of the reference's forward (ground-truth response, regression, dustbins): autograd then adds the gradients that
+    meet in P in the same order, and the fp32 run agrees with the reference's to the last bit or two."""
+    inner = P[..., :-1, :-1]
+    W = inner.shape[-1]
+    out = {}
+    if target is not None:
+        t = target.to(P.dtype).unsqueeze(-1)
+        left, right = torch.floor(t).long().clamp(0, W - 1), torch.ceil(t).long().clamp(0, W - 1)
+        w_right = t - left
+        out["gt"] = (torch.gather(inner, -1, left) * (1 - w_right) + torch.gather(inner, -1, right) * w_right).squeeze(-1)
+    cols = inner.argmax(-1, keepdim=True) + torch.arange(-1, 2)
+    inside = ((cols >= 0) & (cols < W)).to(P.dtype)
+    taps = torch.gather(inner, -1, cols.clamp(0, W - 1)) * inside
+    shift = (torch.arange(W).view(W, 1) - cols).clamp_min(0).to(torch.float32) * inside.float()
+    raw = taps.sum(-1, keepdim=True)
+    forced = mask.unsqueeze(-1) if mask is not None else raw.detach() < 0.1
+    norm = torch.where(forced, torch.ones_like(raw), raw)
+    out["disp"] = (taps / norm * shift).sum(-1)
+    out["occ"] = (1.0 - norm).squeeze(-1)
+    out["norm"] = norm.squeeze(-1)
+    out["bin_l"], out["bin_r"] = P[..., :-1, -1], P[..., -1, :-1]
+    return out, cols[..., 1], forced.squeeze(-1)

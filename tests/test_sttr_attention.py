@@ -5,7 +5,7 @@ on the kernels of csrc/sttr_attention.hip: `ops.sttr_rel_attention`, `models.STT
   tests/golden/sttr_attention_config.py, in fp32 and in fp64, and per tensor d_ref = max|fp32 - fp64| > 0 over the finite entries
   (tests/golden/make_golden_sttr_attention.py).  Tensors of more than WHOLE elements keep d_ref, max|fp64| and a strided subsample
   of the fp64 tensor.
-* Two plain-torch restatements live in this file: 'stock', the reference op for op (the [W, W, C] gather of the table, its
+* Two plain-torch restatements (`attention` of tests/restated.py, `transformer` here): 'stock', the reference op for op (the [W, W, C] gather of the table, its
   projection, three einsums -- also the stock side of tools/sttr_attention_bench.py), and 'table', the form the kernels compute
   (the [2W-1, C] table projected, row (W-1-w) + v read for the pair (w, v)).  Both are pinned to the fixture on the CPU -- in fp64
   to 1e-11 (whole tensors or the subsample), in fp32 to 2 x d_ref -- and the table form then serves as the fp64 oracle of the
@@ -29,7 +29,8 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.sttr_attention_config import (CORE, CORE_GPU_ONLY, TRANSFORMER, TRANSFORMER_GPU_ONLY, core_inputs, core_layout,
                                                 fill_parameters, is_whole, parameter_seed, sine_table, subsample, transformer_inputs,
                                                 transformer_layout, transformer_parameters)
-from tests.parity import GRAD_FACTOR, VALUE_FACTOR, Env, env, on, sync, within  # noqa: F401
+from tests.parity import GRAD_FACTOR, VALUE_FACTOR, Env, env, on, sync, within, within_inf  # noqa: F401
+from tests.restated import attention
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "sttr_attention.npz")
@@ -47,39 +48,6 @@ def finite_sum(x, g):
 
 
 # ------------------------------------------------------------------------------------------ the restatements (plain torch)
-def attention(form, P, prefix, query, key, causal, pos, E):
-    """One MultiheadAttentionRelative call with key = value -> (v_o, attn, raw_attn).  P: parameters by name."""
-    W, B, C = query.shape
-    hd = C // E
-    w_in, b_in = P[prefix + "in_proj_weight"], P[prefix + "in_proj_bias"]
-    if query is key:
-        q, k, v = F.linear(query, w_in, b_in).chunk(3, dim=-1)
-    else:
-        q = F.linear(query, w_in[:C], b_in[:C])
-        k, v = F.linear(key, w_in[C:], b_in[C:]).chunk(2, dim=-1)
-    scaling = float(hd) ** -0.5
-    q = (q * scaling).contiguous().view(W, B, E, hd)
-    k, v = k.contiguous().view(W, B, E, hd), v.contiguous().view(W, B, E, hd)
-    attn = torch.einsum("wnec,vnec->newv", q, k)
-    if pos is not None:
-        idx = (torch.arange(W - 1, -1, -1, device=query.device).view(W, 1) + torch.arange(W, device=query.device).view(1, W)).view(-1)
-        if form == "stock":
-            q_r, k_r = F.linear(torch.index_select(pos, 0, idx).view(W, W, -1), w_in[:2 * C], b_in[:2 * C]).chunk(2, dim=-1)
-            q_r, k_r = (q_r * scaling).contiguous().view(W, W, E, hd), k_r.contiguous().view(W, W, E, hd)
-        else:
-            q_r = (F.linear(pos, w_in[:C], b_in[:C]) * scaling)[idx].view(W, W, E, hd)
-            k_r = F.linear(pos, w_in[C:2 * C], b_in[C:2 * C])[idx].view(W, W, E, hd)
-        attn = attn + torch.einsum("wnec,wvec->newv", q, k_r) + torch.einsum("vnec,wvec->newv", k, q_r)
-    if causal:
-        attn = attn + torch.triu(torch.full((W, W), NINF, dtype=attn.dtype, device=attn.device), 1)
-    raw = attn
-    attn = F.softmax(attn, dim=-1)
-    v_o = torch.bmm(attn.view(B * E, W, W), v.permute(1, 2, 0, 3).reshape(B * E, W, hd))
-    v_o = v_o.reshape(B, E, W, hd).permute(2, 0, 1, 3).reshape(W, B, C)
-    v_o = F.linear(v_o, P[prefix + "out_proj.weight"], P[prefix + "out_proj.bias"])
-    return v_o, attn.sum(dim=1) / E, raw.sum(dim=1)
-
-
 def transformer(form, P, left, right, pos, L, E, checkpointed=False):
     """Transformer.forward -> attn_weight [N, H, W, W]; the left / right split at H * N.  checkpointed: every layer under
     torch.utils.checkpoint, the way the reference runs them."""
@@ -215,13 +183,6 @@ def _want(gold, key, k):
     return (want64 if want64 is not None else _restated64(key)[k]), dref
 
 
-def _within_inf(got, want64, dref, factor, what, log):
-    """tests/parity.within over the finite entries; the -inf entries compared by equality"""
-    inf = torch.isinf(want64)
-    assert torch.equal(got.detach().cpu() == NINF, inf), what
-    within(got.detach().cpu().masked_fill(inf, 0.0), want64.masked_fill(inf, 0.0), dref, factor, what, log)
-
-
 # ------------------------------------------------------------------------------------------ the product vs fp64
 def _core(env, tag, via):
     """The product on a core record, through the module or through ops.sttr_rel_attention between stock projections."""
@@ -266,7 +227,7 @@ def test_attention_matches_reference_fp64(backend, tag, via, gold, parity_log):
     assert set(got) == {k for k, _ in core_layout(tag)}
     for k, shape in core_layout(tag):
         assert tuple(got[k].shape) == shape and got[k].dtype == torch.float32, k
-        _within_inf(got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR,
+        within_inf(got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g_") else VALUE_FACTOR,
                     f"sttr attention {tag} {k} {via} [{backend}]", parity_log)
 
 
@@ -293,7 +254,7 @@ def test_transformer_matches_reference_fp64(backend, tag, gold, parity_log):
     assert set(got) == {k for k, _ in transformer_layout(tag)}
     for k, shape in transformer_layout(tag):
         assert tuple(got[k].shape) == shape, k
-        _within_inf(got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g") else VALUE_FACTOR,
+        within_inf(got[k], *_want(gold, key, k), GRAD_FACTOR if k.startswith("g") else VALUE_FACTOR,
                     f"sttr transformer {tag} {k} [{backend}]", parity_log)
 
 
@@ -311,7 +272,7 @@ def test_batch_of_two_gives_each_samples_record(env, gold, parity_log):  # noqa:
         sync(env)
     for n, tag in enumerate(tags):
         for k, t, f in (("attn_weight", attn, VALUE_FACTOR), ("g_feat_left", left.grad, GRAD_FACTOR), ("g_feat_right", right.grad, GRAD_FACTOR)):
-            _within_inf(t[n:n + 1], *_want(gold, "transformer:" + tag, k), f, f"sttr transformer N=2 sample {n} {k} [{env.name}]", parity_log)
+            within_inf(t[n:n + 1], *_want(gold, "transformer:" + tag, k), f, f"sttr transformer N=2 sample {n} {k} [{env.name}]", parity_log)
 
 
 # ------------------------------------------------------------------------------------------ the op alone

@@ -6,7 +6,8 @@
   keep d_ref, max|fp64| and a strided subsample of the fp64 tensor.  The generator asserts at every pixel that the arg-max is
   separated ((top1 - top2) / top1 >= 1e-3), that the window sum stays 1e-4 away from the 0.1 threshold and that the fp32 and fp64
   runs take the same branch: no pixel is left out of any comparison here.
-* A plain-torch restatement lives in this file and is pinned to the fixture on the CPU first -- in fp64 to 1e-11 (whole tensors or
+* A plain-torch restatement (tests/restated.py: `transported`, `regress`, `target_of`, `constants`) is pinned to the fixture on
+  the CPU first -- in fp64 to 1e-11 (whole tensors or
   the subsample), in fp32 to 2 x d_ref -- and then serves as the fp64 oracle of the subsampled tensors.
 * The product (emulator build here, gfx950 with `-m gpu`) is compared with fp64: values within VALUE_FACTOR (2) x d_ref, gradients
   within GRAD_FACTOR (3) x d_ref, floor 2e-7 * max(1, max|want|) where d_ref is zero.  Every element of every tensor is compared
@@ -29,6 +30,7 @@ from tests.backends import be, ptr  # noqa: F401
 from tests.golden.sttr_config import (CASE_VARIANTS, CASES, FORWARD_CASES, FORWARD_KEYS, GPU_ONLY, OUTPUTS, SCALE, SUBSAMPLE, VARIANTS,
                                       StandInCal, forward_inputs, inputs, is_whole, layout, losses, outputs_of, subsample)
 from tests.parity import GRAD_FACTOR, VALUE_FACTOR, Env, env, on, pin, pin_subsample, sync, within, within_fixture  # noqa: F401
+from tests.restated import constants, regress, target_of, transported
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sttr_head.npz")
 RECORDS = [(tag, var) for tag in CASES for var in CASE_VARIANTS[tag]]
@@ -52,56 +54,6 @@ def _case_inputs(tag, var):
 
 
 # ------------------------------------------------------------------------------------------ the restatement (plain torch)
-def constants(W):
-    """log mu = log nu and log 2W: fp32 host tensors, in an fp64 run as well"""
-    return (torch.cat([torch.ones(W), torch.tensor([W]).float()]) / (2 * W)).log(), torch.log(torch.tensor([2.0 * W]))
-
-
-def transported(attn, phi, ot, iters):
-    """[N, H, W, W] -> P [N, H, W+1, W+1]"""
-    N, H, W, _ = attn.shape
-    S = torch.cat([torch.cat([attn, phi.expand(N, H, W, 1)], -1), phi.expand(N, H, 1, W + 1)], -2)
-    if not ot:
-        return torch.softmax(S, dim=-1)
-    lm, l2w = constants(W)
-    u = torch.zeros(N, H, W + 1, dtype=attn.dtype)
-    for _ in range(iters):
-        v = lm - torch.logsumexp(S + u.unsqueeze(3), dim=2)
-        u = lm - torch.logsumexp(S + v.unsqueeze(2), dim=3)
-    return (S + u.unsqueeze(3) + v.unsqueeze(2) + l2w).exp()
-
-
-def target_of(disp_gt):
-    """full-resolution ground truth [N, 3H, 3W] -> the right position of every sampled pixel in low-resolution columns"""
-    w = disp_gt.shape[-1]
-    return _low(torch.arange(w, dtype=torch.float32) - disp_gt) / float(SCALE)
-
-
-def regress(P, mask, target):
-    """P [N, H, W+1, W+1] -> the five outputs ('gt' only with a target), the arg-max and where norm was forced.  The steps come in
-    the order of the reference's forward (ground-truth response, regression, dustbins): autograd then adds the gradients that
-    meet in P in the same order, and the fp32 run agrees with the reference's to the last bit or two."""
-    inner = P[..., :-1, :-1]
-    W = inner.shape[-1]
-    out = {}
-    if target is not None:
-        t = target.to(P.dtype).unsqueeze(-1)
-        left, right = torch.floor(t).long().clamp(0, W - 1), torch.ceil(t).long().clamp(0, W - 1)
-        w_right = t - left
-        out["gt"] = (torch.gather(inner, -1, left) * (1 - w_right) + torch.gather(inner, -1, right) * w_right).squeeze(-1)
-    cols = inner.argmax(-1, keepdim=True) + torch.arange(-1, 2)
-    inside = ((cols >= 0) & (cols < W)).to(P.dtype)
-    taps = torch.gather(inner, -1, cols.clamp(0, W - 1)) * inside
-    shift = (torch.arange(W).view(W, 1) - cols).clamp_min(0).to(torch.float32) * inside.float()
-    raw = taps.sum(-1, keepdim=True)
-    forced = mask.unsqueeze(-1) if mask is not None else raw.detach() < 0.1
-    norm = torch.where(forced, torch.ones_like(raw), raw)
-    out["disp"] = (taps / norm * shift).sum(-1)
-    out["occ"] = (1.0 - norm).squeeze(-1)
-    out["bin_l"], out["bin_r"] = P[..., :-1, -1], P[..., -1, :-1]
-    return out, cols[..., 1], forced.squeeze(-1)
-
-
 def _restated(tag, var, dtype):
     ot = VARIANTS[var][0]
     iters = CASES[tag][3]

@@ -459,6 +459,63 @@ def test_bn_finalize(be, verdict, case):
     verdict.done()
 
 
+FG_CASES = [(g, C, n) for g in (1, 2, 3) for C in (16, 40) for n in (1, 7)]      # groups, C, nrows: one slab, the two views, an odd count;
+#                                                                                  C = 40 is no power of two; a single row, and several
+
+
+@pytest.mark.parametrize("case", FG_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_bn_finalize_groups(be, verdict, case):
+    """stx_bn_finalize_groups: out [4][groups][C] against fp64 from the partial sums, the running statistics updated slab after
+    slab; every bit equal to `groups` successive calls of stx_bn_finalize on the slabs (the header's promise), with the running
+    buffers and with both running pointers NULL."""
+    groups, C, nrows = case
+    g = _gen(60 + FG_CASES.index(case))
+    part = _randn(g, groups, nrows, 2, C)
+    part[:, :, 1] = part[:, :, 1].abs() * 40 + 50    # sum z^2 comfortably above (sum z)^2 / n
+    count = float(nrows * 64)
+    gamma, beta, rm, rv = torch.rand(C, generator=g) + 0.5, _randn(g, C), _randn(g, C), torch.rand(C, generator=g) + 0.5
+
+    def slabs(dt):
+        m, v, rows = rm.to(dt), rv.to(dt), []
+        for k in range(groups):
+            *four, m, v = _finalize(part[k].to(dt), count, gamma.to(dt), beta.to(dt), m, v)
+            rows.append(torch.stack(four))
+        return torch.stack(rows, 1), m, v                                     # [4][groups][C], and the buffers behind the last slab
+    with _one_thread():
+        w64, w32 = slabs(torch.float64), slabs(torch.float32)
+    what = f"bn_finalize_groups[{be.name}:{groups}x{C}x{nrows}]"
+    Gd = Guards(be)
+    dpart, dgamma, dbeta = Gd.inp(part), Gd.inp(gamma), Gd.inp(beta)
+
+    def run(name, running):
+        bufs = [Gd.out(C), Gd.out(C)] if running else [None, None]
+        for b, t in zip(bufs, (rm, rv)):
+            if b is not None:
+                b.copy_(t)
+        out = Gd.out(4, groups, C)
+        if name == "stx_bn_finalize_groups":
+            be.call(name, dpart, nrows, C, count, dgamma, dbeta, *bufs, 0.1, 1e-5, out, groups)
+            Gd.check(f"{what}:{name}")
+        else:
+            one = [Gd.out(C) for _ in range(4)]
+            for k in range(groups):
+                be.call(name, dpart[k], nrows, C, count, dgamma, dbeta, *bufs, 0.1, 1e-5, *one)
+                Gd.check(f"{what}:{name}:{k}")
+                for i in range(4):
+                    out[i, k].copy_(one[i])
+        return [out.cpu()] + [None if b is None else b.cpu() for b in bufs]
+    got = run("stx_bn_finalize_groups", True)
+    for i, name in enumerate(("scale", "shift", "mean", "invstd")):
+        verdict.within(got[0][i], w64[0][i], _dist(w32[0][i], w64[0][i]), VALUE_FACTOR, f"{what}:{name}")
+    verdict.within(got[1], w64[1], _dist(w32[1], w64[1]), VALUE_FACTOR, f"{what}:rm")
+    verdict.within(got[2], w64[2], _dist(w32[2], w64[2]), VALUE_FACTOR, f"{what}:rv")
+    for a, b in zip(got, run("stx_bn_finalize", True)):
+        assert torch.equal(a, b), what
+    plain, plain_slabs = run("stx_bn_finalize_groups", False), run("stx_bn_finalize", False)
+    assert torch.equal(plain[0], got[0]) and torch.equal(plain_slabs[0], got[0]), what
+    verdict.done()
+
+
 BN_CASES = {
     # nvox, C, second BatchNorm branch, activation code, plain residual
     "1000x32_relu": (1000, 32, False, 1, False),
