@@ -10,7 +10,6 @@ import os
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from stereo_toolbox_amd.utils import synthetic_tensor
 
@@ -62,32 +61,9 @@ def sinusoid(L, C, dtype):
 
 
 def encoder(x, pe, params, heads, eps=1e-5, masks=None, scale=1.0, norm_inputs=None):
-    """The layers in plain torch, any dtype.  x [N, L, C]; params: 16 tensors per layer in state-dict order; masks: None or
-    [layers, 3, N, L, max(C, ff)] keep decisions, applied with `scale` = 1 / (1 - p).  `norm_inputs`: a list that receives every
-    LayerNorm input."""
-    N, L, C = x.shape
-    hd = C // heads
-    if pe is not None:
-        x = x + pe[None]
-    for i in range(len(params) // 16):
-        qw, qb, kw, kb, vw, vb, ow, ob, w1, b1, w2, b2, g1, e1, g2, e2 = params[16 * i:16 * i + 16]
-        ff = w1.shape[0]
-
-        def drop(t, site, width):
-            return t if masks is None else t * (masks[i, site, :, :, :width].to(t.dtype) * scale)
-        q = F.linear(x, qw, qb).view(N, L, heads, hd).transpose(1, 2)
-        k = F.linear(x, kw, kb).view(N, L, heads, hd).transpose(1, 2)
-        v = F.linear(x, vw, vb).view(N, L, heads, hd).transpose(1, 2)
-        a = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(hd), dim=-1) @ v
-        z = x + drop(F.linear(a.transpose(1, 2).reshape(N, L, C), ow, ob), 0, C)
-        if norm_inputs is not None:
-            norm_inputs.append(z)
-        x = F.layer_norm(z, (C,), g1, e1, eps)
-        z = x + drop(F.linear(drop(F.gelu(F.linear(x, w1, b1)), 1, ff), w2, b2), 2, C)
-        if norm_inputs is not None:
-            norm_inputs.append(z)
-        x = F.layer_norm(z, (C,), g2, e2, eps)
-    return x
+    """The layers in plain torch, any dtype: tests/restated.py::disp_encoder (shared with the kernel-level parity module)."""
+    from tests.restated import disp_encoder
+    return disp_encoder(x, pe, params, heads, eps=eps, masks=masks, scale=scale, norm_inputs=norm_inputs)
 
 
 def to_sequences(cv):

@@ -1,7 +1,8 @@
 """Plain-torch restatements of reference code that more than one test module compares with: the gather form (no grid_sample)
 of IGEV's geometry lookup (reference models/IGEVStereo/geometry.py:7-70) and convex upsampling (submodule.py:243-255), and
 StereoAnywhere's truncation mask (utils/utils.py:216-238), STTR's attention with relative positions (models/STTR/attention.py) and its
-matching head (models/STTR/regression_head.py).  A restatement used by a single test module lives in that module.
+matching head (models/STTR/regression_head.py), the encoder layers of FoundationStereo's disparity transformer (submodule.py
+`FlashAttentionTransformerEncoderLayer`).  A restatement used by a single test module lives in that module.
 """
 import math
 
@@ -213,3 +214,55 @@ def regress(P, mask, target):
     out["norm"] = norm.squeeze(-1)
     out["bin_l"], out["bin_r"] = P[..., :-1, -1], P[..., -1, :-1]
     return out, cols[..., 1], forced.squeeze(-1)
+
+
+# ------------------------------------------------------------------------------------------ FoundationStereo: disparity transformer
+DISP_ENCODER_MISSES = ("unbiased", "tanh_gelu", "over_hd", "pe_every_layer", "pre_norm", "query_softmax", "site1_at_site2")
+
+
+def disp_encoder(x, pe, params, heads, eps=1e-5, masks=None, scale=1.0, norm_inputs=None, miss=None):
+    """The layers in plain torch, any dtype.  x [N, L, C]; params: 16 tensors per layer in state-dict order; masks: None or
+    [layers, 3, N, L, max(C, ff)] keep decisions, applied with `scale` = 1 / (1 - p).  `norm_inputs`: a list that receives every
+    LayerNorm input.  `miss`: None, or one of DISP_ENCODER_MISSES -- a subtly different layer that the parity rule has to refuse
+    (unbiased LayerNorm variance; tanh GELU; scores over hd instead of sqrt(hd); pe in front of every layer; pre-norm order;
+    soft-max over the query axis; the masks of site 1 used at site 2)."""
+    assert miss is None or miss in DISP_ENCODER_MISSES, miss
+    N, L, C = x.shape
+    hd = C // heads
+
+    def norm(z, g, e):
+        if norm_inputs is not None:
+            norm_inputs.append(z)
+        if miss != "unbiased":
+            return F.layer_norm(z, (C,), g, e, eps)
+        return (z - z.mean(-1, keepdim=True)) / torch.sqrt(z.var(-1, unbiased=True, keepdim=True) + eps) * g + e
+    if pe is not None and miss != "pe_every_layer":
+        x = x + pe[None]
+    for i in range(len(params) // 16):
+        qw, qb, kw, kb, vw, vb, ow, ob, w1, b1, w2, b2, g1, e1, g2, e2 = params[16 * i:16 * i + 16]
+        ff = w1.shape[0]
+
+        def drop(t, site, width):
+            return t if masks is None else t * (masks[i, site, :, :, :width].to(t.dtype) * scale)
+
+        def attend(t):
+            q = F.linear(t, qw, qb).view(N, L, heads, hd).transpose(1, 2)
+            k = F.linear(t, kw, kb).view(N, L, heads, hd).transpose(1, 2)
+            v = F.linear(t, vw, vb).view(N, L, heads, hd).transpose(1, 2)
+            s = q @ k.transpose(-1, -2) / (hd if miss == "over_hd" else math.sqrt(hd))
+            a = torch.softmax(s, dim=-2 if miss == "query_softmax" else -1) @ v
+            return drop(F.linear(a.transpose(1, 2).reshape(N, L, C), ow, ob), 0, C)
+
+        def feed(t):
+            h = F.linear(t, w1, b1)
+            h = F.gelu(h, approximate="tanh") if miss == "tanh_gelu" else F.gelu(h)
+            return drop(F.linear(drop(h, 1, ff), w2, b2), 1 if miss == "site1_at_site2" else 2, C)
+        if pe is not None and miss == "pe_every_layer":
+            x = x + pe[None]
+        if miss == "pre_norm":
+            x = x + attend(norm(x, g1, e1))
+            x = x + feed(norm(x, g2, e2))
+            continue
+        x = norm(x + attend(x), g1, e1)
+        x = norm(x + feed(x), g2, e2)
+    return x

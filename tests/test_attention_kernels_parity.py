@@ -1,8 +1,8 @@
 """The kernels of STTR's transformer and matching head under the fp64 parity rule, in guard bands: sttr_attention.hip, sttr_head.hip.
 (The benchmarked train step: tests/test_conv3d_parity.py and tests/test_train_kernels_parity.py; the iterative families:
 tests/test_iterative_kernels_parity.py.)  This is the first of two parts: the cases of these two files alone are 982 (case, tensor)
-pairs, each a line of the recorded d_ref table; disp_attention.hip and conv3d_axial.hip -- some 1200 pairs more, with their own
-restatements, layouts and near misses -- follow in a module of their own and are under no kernel-level rule until then.
+pairs, each a line of the recorded d_ref table; disp_attention.hip and conv3d_axial.hip -- 508 pairs more, with their own
+restatements, layouts and near misses -- are held to the same rule by tests/test_foundation_kernels_parity.py.
 
 The rule (tests/parity.py::within), for every call: `want64` is the operation in fp64 on the CPU from the same fp32 inputs cast up
 (the tests/restated.py restatements and autograd through them), `d_ref` =
