@@ -210,6 +210,90 @@ int stx_convgru_wgrad(const float* s0, int c0, int p0, const float* s1, int c1, 
                       const float* s3, int c3, int p3, const float* g0, const float* g1, int CG, float* dw, float* workspace,
                       int B, int H, int W, void* stream);
 
+/* ---- Selective recurrent unit (csrc/selgru.hip) ------------------------------------------------------
+ * SelectiveConvGRU of SelectiveStereo (reference SelectiveStereo/SelectiveRAFT/update.py:15-71, the same text in SelectiveIGEV):
+ * h' = att h_s + (1 - att) h_l with h_s a RaftConvGRU of 1x1 kernels and h_l one of 3x3 kernels (the 3x3 cell is the stx_convgru_*
+ * entry points with NULL context biases).  These entry points are the 1x1 cell, the blend and its gradient.  Layout, the SOURCE
+ * lists and the limits are those of the ConvGRU block above (stx_selgru_supported(hidden, nx, cx0, cx1, cx2)); a 1x1 kernel sees
+ * no neighbours, so the pixels are one flat axis of P = B H W.
+ * stx_selgru_pack_weight: packs one or two (w1 may be NULL) torch weights [A][Bd][1][1], stacked along A, into
+ *   stx_selgru_packed_floats(K, N) floats; mode 0: forward (K = Bd, N = A or 2 A); mode 1: data gradient (transposed channels:
+ *   K = A or 2 A, N = Bd).
+ * stx_selgru_gemm: acc[pix][n] = sum over the source list with packed weights of N output channels, then the epilogue `epi`:
+ *   0 raw: out0[pix][out_pitch] = (acc + add0[pix][add0_pitch]) + add1[pix][add1_pitch] (each may be NULL; out0 may be either);
+ *   1 zr:  N = 2 split (split = hidden): out0 = z = sigmoid(acc + bias0), out1 = r h with r = sigmoid(acc + bias1), out2 = r
+ *          (may be NULL);
+ *   2 q:   N = split: q = tanh(acc + bias0), mine = (1 - z) h + z q, out1 = q (may be NULL), and with `blend`
+ *          0: out0 = mine;  1: out0 = att mine + (1 - att) other;  2: out0 = att other + (1 - att) mine
+ *          (att [pix], other [pix][hidden] = the other cell's state; out0 may be `other`: the blend is formed in place).
+ *   Pre-activations, gates, the convex update and the blend are formed in double and rounded once.  Outputs never alias h.
+ * stx_selgru_blend_bwd: gs = att g, gl = (1 - att) g dense [pix][hidden]; gatt (may be NULL) [pix] = sum_c g (h_s - h_l) with
+ *   h_s, h_l re-formed from zs, qs, zl, ql and h, summed in double in channel order.
+ * stx_selgru_wgrad: dw[(1 or 2) CG][K] from the source list against the dense maps g0 (and g1, may be NULL) [pix][CG]; partial
+ *   sums in `workspace` (stx_selgru_wgrad_workspace_floats(P, K, CC = rows of dw) floats), fixed-order reduction.
+ * stx_selgru_col_sum: out[k][n] = column sums of up to three dense maps [pix][n] (trailing ones may be NULL), in double, rounded
+ *   once: the bias gradients from gq, gz, gr; `workspace` of stx_selgru_col_sum_workspace_floats(P, n) floats, 8-byte aligned.
+ * The gate / reset backward of a 1x1 cell are stx_convgru_gate_bwd / _reset_bwd (their partial rows may be NULL).
+ * No atomics: every result is bitwise reproducible.  Unsupported arguments return an error (the queries 0) and launch nothing. */
+int stx_selgru_supported(int hidden, int nx, int cx0, int cx1, int cx2);
+long long stx_selgru_packed_floats(int K, int N);
+int stx_selgru_pack_weight(const float* w0, const float* w1, float* wp, int A, int Bd, int mode, void* stream);
+int stx_selgru_gemm(const float* s0, int c0, int p0, const float* s1, int c1, int p1, const float* s2, int c2, int p2,
+                    const float* s3, int c3, int p3, const float* wp, int N, int epi, int split, const float* bias0,
+                    const float* bias1, const float* add0, int add0_pitch, const float* add1, int add1_pitch, const float* h,
+                    int h_pitch, const float* z, const float* att, const float* other, int blend, float* out0, float* out1,
+                    float* out2, int out_pitch, long long P, void* stream);
+int stx_selgru_blend_bwd(const float* g, int g_pitch, const float* att, const float* zs, const float* qs, const float* zl,
+                         const float* ql, const float* h, int h_pitch, float* gs, float* gl, float* gatt, long long P, int hidden,
+                         void* stream);
+long long stx_selgru_col_sum_workspace_floats(long long P, int n);
+int stx_selgru_col_sum(const float* m0, const float* m1, const float* m2, float* out, double* workspace, long long P, int n,
+                       void* stream);
+long long stx_selgru_wgrad_workspace_floats(long long P, int K, int CC);
+int stx_selgru_wgrad(const float* s0, int c0, int p0, const float* s1, int c1, int p1, const float* s2, int c2, int p2,
+                     const float* s3, int c3, int p3, const float* g0, const float* g1, int CG, float* dw, float* workspace,
+                     long long P, void* stream);
+
+/* ---- Contextual spatial attention (csrc/csa.hip) -----------------------------------------------------
+ * ChannelAttentionEnhancement and SpatialAttentionExtractor of SelectiveStereo (reference SelectiveStereo/SelectiveRAFT/update.py:
+ * 106-135), used as `x' = cam(x) x; att = sam(x')`: gate = sigmoid(W2 relu(W1 avg) + W2 relu(W1 max)) over the global average /
+ * max pools of x, W1 [C/16][C], W2 [C][C/16]; att = sigmoid(conv_kxk([mean_c x' | max_c x'])) with w [2][k][k], zero padding k / 2.
+ * x is channels-last fp32 [B][HW][pitch >= C]; served (stx_csa_supported(C, k)): C a multiple of 16 up to 256, k odd up to 7.
+ * All sums and products are formed in double and rounded once.  Ties of a max go to the lowest pixel (global pool) / the lowest
+ * channel (per pixel).  No atomics: partials per workgroup, combined in a fixed order.
+ * stx_csa_pool:  partials psum (double) / pmax / pidx [B][nblk][C], nblk = stx_csa_blocks(HW, C).
+ * stx_csa_gate:  the gate [B][C] from the partials by one workgroup per batch item, with pooled [B][2][C] (double, avg | max) and
+ *   argp [B][C] (arg max pixel) for the backward pass.
+ * stx_csa_apply: xp = x' = gate x dense [B][HW][C], map [B][HW][2] = channel mean | max of x', argc [B][HW] the arg max channel
+ *   (may be NULL); every workgroup recomputes the gate from the partials; gate / pooled / argp (all or none) as stx_csa_gate
+ *   leaves them.  With w1 NULL there is no gate: map / argc are those of x itself.
+ * stx_csa_sam:   att [B][H][W] from map and w.
+ * stx_csa_sam_bwd: from g = dL/d att: gpre (scratch [B][H][W]), gmap [B][H][W][2] and dw [2][k][k] (may be NULL; else `workspace`
+ *   of stx_csa_sam_bwd_workspace_floats floats, 8-byte aligned).
+ * stx_csa_apply_bwd: g_x' = gxp (may be NULL) + the map's gradient gmap through mean and arg max (may be NULL, else with argc);
+ *   gx = gate g_x' dense [B][HW][C] (gate NULL: g_x'), pgate (may be NULL) [B][nblk][C] doubles = partial sums of g_x' x.
+ * stx_csa_gate_bwd: one workgroup: from the gate's gradient -- the partials pgate, or gg [B][C] floats -- and pooled: dw1, dw2 (may
+ *   be NULL), gavg [B][C] (per pixel, 1 / HW folded in) and gmx [B][C] (to the arg max pixel).
+ * stx_csa_pool_bwd: gx[b][pix][c] (+)= gavg + (pix == argp) gmx. */
+int stx_csa_supported(int C, int ksize);
+int stx_csa_blocks(long long HW, int C);
+int stx_csa_pool(const float* x, int pitch, double* psum, float* pmax, int* pidx, int B, long long HW, int C, void* stream);
+int stx_csa_gate(const double* psum, const float* pmax, const int* pidx, int nblk, const float* w1, const float* w2, float* gate,
+                 double* pooled, int* argp, int B, long long HW, int C, void* stream);
+int stx_csa_apply(const float* x, int pitch, const double* psum, const float* pmax, const int* pidx, int nblk, const float* w1,
+                  const float* w2, float* xp, float* map, int* argc, float* gate, double* pooled, int* argp, int B, long long HW,
+                  int C, void* stream);
+int stx_csa_sam(const float* map, const float* w, float* att, int B, int H, int W, int ksize, void* stream);
+long long stx_csa_sam_bwd_workspace_floats(int B, int H, int W, int ksize);
+int stx_csa_sam_bwd(const float* g, const float* att, const float* map, const float* w, float* gpre, float* gmap, float* dw,
+                    double* workspace, int B, int H, int W, int ksize, void* stream);
+int stx_csa_apply_bwd(const float* x, int pitch, const float* gate, const float* gxp, int gxp_pitch, const float* gmap,
+                      const int* argc, float* gx, double* pgate, int B, long long HW, int C, void* stream);
+int stx_csa_gate_bwd(const double* pgate, int nblk, const float* gg, const double* pooled, const float* w1, const float* w2,
+                     float* dw1, float* dw2, float* gavg, float* gmx, int B, long long HW, int C, void* stream);
+int stx_csa_pool_bwd(float* gx, const float* gavg, const float* gmx, const int* argp, int accumulate, int B, long long HW, int C,
+                     void* stream);
+
 /* 3x3 stride-1 Conv2d (padding 1, no bias), channels-last, of the 2-D feature CNN's BasicBlocks with 32 / 64 channels: forward
  * and data gradient (reference models/GwcNet/gwcnet.py:12-42 `convbn(in, out, 3, 1, pad, 1)` -> nn.Conv2d at 1/2 and 1/4
  * resolution; PSMNet/submodule.py:57-97; ACVNet/acv.py:15-40).  x [B][H][W][Cin], out [B][H][W][Cout], fp32.

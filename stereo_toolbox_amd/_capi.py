@@ -75,6 +75,28 @@ SIGNATURES = {
     "stx_convgru_row_sum": [_P, _P, _I, _I, _P],
     "stx_convgru_wgrad_workspace_floats": [_I] * 5,
     "stx_convgru_wgrad": [_P, _I, _I] * 4 + [_P, _P, _I, _P, _P, _I, _I, _I, _P],
+    # selgru.hip
+    "stx_selgru_supported": [_I] * 5,
+    "stx_selgru_packed_floats": [_I, _I],
+    "stx_selgru_pack_weight": [_P, _P, _P, _I, _I, _I, _P],
+    "stx_selgru_gemm": [_P, _I, _I] * 4 + [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _L, _P],
+    "stx_selgru_blend_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _I, _P],
+    "stx_selgru_col_sum_workspace_floats": [_L, _I],
+    "stx_selgru_col_sum": [_P, _P, _P, _P, _P, _L, _I, _P],
+    "stx_selgru_wgrad_workspace_floats": [_L, _I, _I],
+    "stx_selgru_wgrad": [_P, _I, _I] * 4 + [_P, _P, _I, _P, _P, _L, _P],
+    # csa.hip
+    "stx_csa_supported": [_I, _I],
+    "stx_csa_blocks": [_L, _I],
+    "stx_csa_pool": [_P, _I, _P, _P, _P, _I, _L, _I, _P],
+    "stx_csa_gate": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _L, _I, _P],
+    "stx_csa_apply": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P],
+    "stx_csa_sam": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "stx_csa_sam_bwd_workspace_floats": [_I] * 4,
+    "stx_csa_sam_bwd": [_P] * 8 + [_I] * 4 + [_P],
+    "stx_csa_apply_bwd": [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _L, _I, _P],
+    "stx_csa_gate_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P],
+    "stx_csa_pool_bwd": [_P, _P, _P, _P, _I, _I, _L, _I, _P],
     # conv2d.hip
     "stx_conv2d_supported": [_I, _I],
     "stx_conv2d_stat_rows": [_I],

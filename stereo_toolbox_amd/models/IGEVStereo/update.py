@@ -4,7 +4,7 @@
 RAFTStereo/update.py:16-32, DEFOMStereo/update.py:18-37, StereoAnywhere/update.py:46-62 and FoundationStereo/update.py:33-47:
 same constructor, forward signature and state-dict keys (`convz / convr / convq . weight / bias`), so their checkpoints load.
 One class object serves all five packages.  The rest of the update blocks (motion encoders, heads, pool2x / interp,
-BasicMultiUpdateBlock, SepConvGRU, RaftConvGRU / SelectiveConvGRU) is not built.
+BasicMultiUpdateBlock, SepConvGRU) is not built; RaftConvGRU / SelectiveConvGRU live in models/SelectiveStereo.
 """
 import torch.nn as nn
 

@@ -13,6 +13,7 @@ from . import DEFOMStereo  # noqa: F401  (correlation block only)
 from . import StereoAnywhere  # noqa: F401  (volume-in correlation block and volume estimators only)
 from . import STTR  # noqa: F401  (transformer and regression head)
 from . import MonSter  # noqa: F401  (mono / stereo mutual refinement: scale-shift fit and feature flaws)
+from . import SelectiveStereo  # noqa: F401  (selective recurrent unit and contextual spatial attention)
 
 
 def load_checkpoint_flexible(model, checkpoint_path, state_dict_key=None):

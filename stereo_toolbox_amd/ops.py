@@ -718,18 +718,18 @@ def _cl_source(t):
     return t, pitch
 
 
-def _convgru_chk(t, name, like=None, channels=None):
+def _convgru_chk(t, name, like=None, channels=None, who="convgru"):
     if t is None:
         return
     if not on_device(t):
-        raise StxError(f"convgru: {name}: expected a ROCm device tensor, got {t.device} -- the cell has no CPU fallback")
+        raise StxError(f"{who}: {name}: expected a ROCm device tensor, got {t.device} -- the cell has no CPU fallback")
     if t.dtype != torch.float32:
-        raise StxError(f"convgru: {name}: expected float32, got {t.dtype}")
+        raise StxError(f"{who}: {name}: expected float32, got {t.dtype}")
     if like is not None:
         if t.dim() != 4 or t.shape[0] != like.shape[0] or tuple(t.shape[2:]) != tuple(like.shape[2:]):
-            raise StxError(f"convgru: {name} has shape {tuple(t.shape)}, h has {tuple(like.shape)} (batch, H and W must agree)")
+            raise StxError(f"{who}: {name} has shape {tuple(t.shape)}, h has {tuple(like.shape)} (batch, H and W must agree)")
         if channels is not None and t.shape[1] != channels:
-            raise StxError(f"convgru: {name} has {t.shape[1]} channels, expected {channels}")
+            raise StxError(f"{who}: {name} has {t.shape[1]} channels, expected {channels}")
 
 
 def _convgru_pack(w0, w1, mode):
@@ -947,6 +947,507 @@ def convgru(h, cz, cr, cq, x_list, wz, bz, wr, br, wq, bq):
         raise StxError(f"convgru: hidden {hidden} (a multiple of 16, <= {CONVGRU_MAX_HIDDEN}) with x channels {cx} (multiples of 4, "
                        f"hidden + sum <= {CONVGRU_MAX_K}) is not served")
     return ConvGRUFn.apply(h, cz, cr, cq, wz, bz, wr, br, wq, bq, *x_list)
+
+
+# ------------------------------------------------------------------------------ SelectiveStereo cells (selgru.hip + convgru.hip)
+SELGRU_PACKS = 0             # pack launches of 1x1 weights so far (the 3x3 ones count in CONVGRU_PACKS)
+
+
+def _selgru_pack(w0, w1, mode, n_out=None):
+    """Packed copy of one or two 1x1 RaftConvGRU weights [hidden][K][1][1] (mode 0: forward, 1: data gradient; `n_out`: mode 1
+    restricted to the first n_out output channels, the data gradient of h alone); cached like the ConvGRU packs."""
+    global SELGRU_PACKS
+    key = tuple(v for w in (w0, w1) if w is not None for v in (w._version, w.data_ptr()))
+    tag = ("selgru", mode, w1 is not None, n_out)
+    if _CACHE_ENABLED:
+        cache = w0.__dict__.setdefault("_stx_packed", {})
+        hit = cache.get(tag)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+    cut = lambda w: None if w is None else (w.detach() if n_out is None else w.detach()[:, :n_out]).contiguous()   # noqa: E731
+    w0c, w1c = cut(w0), cut(w1)
+    A, Bd = w0c.shape[0], w0c.shape[1]
+    nw = 1 if w1 is None else 2
+    K, N = (Bd, nw * A) if mode == 0 else (nw * A, Bd)
+    n = get_lib().raw("stx_selgru_packed_floats")(K, N)
+    if n <= 0:
+        raise StxError(f"raft_convgru: GEMM-K {K} (a multiple of 4, <= {CONVGRU_MAX_K}) x N {N} unsupported")
+    wp = torch.empty(n, dtype=torch.float32, device=w0.device)
+    _call("stx_selgru_pack_weight", _p(w0c), _p(w1c), _p(wp), A, Bd, mode)
+    SELGRU_PACKS += 1
+    if _CACHE_ENABLED:
+        cache[tag] = (key, wp)
+    return wp
+
+
+def _raft_pack(ks, w0, w1, mode, n_out=None):
+    if ks == 1:
+        return _selgru_pack(w0, w1, mode, n_out)
+    return _convgru_pack(w0, w1, mode) if n_out is None else _convgru_pack_head(w0, w1, n_out)
+
+
+def _raft_gemm(ks, srcs, wp, N, B, H, W, epi=0, split=0, bias0=None, bias1=None, add0=None, add1=None, h=None, z=None, att=None,
+               other=None, blend=0, out0=None, out1=None, out2=None, out_pitch=0):
+    """One GEMM launch of a RaftConvGRU cell: the 3x3 kernel of convgru.hip or the 1x1 kernel of selgru.hip (which alone takes a
+    second raw addend and the blend)."""
+    if ks == 3:
+        assert blend == 0 and add1 is None
+        return convgru_gemm(srcs, wp, N, B, H, W, epi=epi, split=split, bias0=bias0, bias1=bias1, add0=add0, h=h, z=z, out0=out0,
+                            out1=out1, out2=out2, out_pitch=out_pitch)
+    a0, a0p = add0 if add0 is not None else (None, 0)
+    a1, a1p = add1 if add1 is not None else (None, 0)
+    ht, hp = h if h is not None else (None, 0)
+    _call("stx_selgru_gemm", *_src_args(srcs), _p(wp), N, epi, split, _p(bias0), _p(bias1), _p(a0), a0p, _p(a1), a1p, _p(ht), hp,
+          _p(z), _p(att), _p(other), blend, _p(out0), _p(out1), _p(out2), out_pitch, B * H * W)
+
+
+def _raft_cell_fwd(ks, hs, xsrc, w, need, att=None, other=None, blend=0):
+    """z, r, q, r h and the new state of one RaftConvGRU cell (r, q only with `need`); with `blend` the state is blended with
+    `other` in place (stx_selgru_gemm)."""
+    wz, bz, wr, br, wq, bq = w
+    B, hidden, H, W = hs[0].shape
+    new = lambda: torch.empty(B, H, W, hidden, dtype=torch.float32, device=hs[0].device)       # noqa: E731
+    z, rh = new(), new()
+    r = new() if need else None
+    q = new() if need else None
+    hn = other if blend else new()
+    bzc, brc, bqc = (None if b is None else b.detach().contiguous() for b in (bz, br, bq))
+    _raft_gemm(ks, [hs] + xsrc, _raft_pack(ks, wz, wr, 0), 2 * hidden, B, H, W, epi=1, split=hidden, bias0=bzc, bias1=brc, h=hs,
+               out0=z, out1=rh, out2=r)
+    _raft_gemm(ks, [(_nchw(rh), hidden)] + xsrc, _raft_pack(ks, wq, None, 0), hidden, B, H, W, epi=2, split=hidden, bias0=bqc,
+               h=hs, z=z, att=att, other=other if blend else None, blend=blend, out0=hn, out1=q)
+    return z, r, q, rh, hn
+
+
+def _raft_cell_bwd(ks, g, h, z, r, q, rh, xsrc, w, need_x, need_w, need_b, prev=None):
+    """The backward chain of one RaftConvGRU cell for the incoming gradient g (tensor, pitch): gate backward, q data gradient,
+    reset backward, z | r data gradient, weight gradients, bias gradients as column sums of gq, gz, gr.  Returns buf [B][H][W][hidden (+ K_x with need_x)] = [dL/dh | g_x] -- with `prev` (1x1
+    cells only) the other cell's buffer is added: (product + own partial) + prev --, the weight gradients (wz, wr, wq) and the
+    bias gradients (bz, br, bq), None where not needed."""
+    gt, gp = g
+    ht, hp = h
+    wz, wr, wq = w
+    B, hidden, H, W = ht.shape
+    dev = ht.device
+    P = B * H * W
+    K = hidden + sum(t.shape[1] for t, _ in xsrc)
+    Ndg = K if need_x else hidden
+    new = lambda: torch.empty(B, H, W, hidden, dtype=torch.float32, device=dev)       # noqa: E731
+    gq, gz, gr = new(), new(), new()
+    _call("stx_convgru_gate_bwd", _p(gt), gp, _p(z), _p(q), _p(ht), hp, _p(gq), _p(gz), None, P, hidden)
+    buf = torch.empty(B, H, W, Ndg, dtype=torch.float32, device=dev)
+    n_out = None if need_x else hidden
+    _raft_gemm(ks, [(_nchw(gq), hidden)], _raft_pack(ks, wq, None, 1, n_out), Ndg, B, H, W, out0=buf, out_pitch=Ndg)
+    _call("stx_convgru_reset_bwd", _p(buf), Ndg, _p(gt), gp, _p(z), _p(r), _p(ht), hp, _p(gr), None, P, hidden)
+    _raft_gemm(ks, [(_nchw(gz), hidden), (_nchw(gr), hidden)], _raft_pack(ks, wz, wr, 1, n_out), Ndg, B, H, W, add0=(buf, Ndg),
+               add1=None if prev is None else (prev, Ndg), out0=buf, out_pitch=Ndg)
+    dw = [None, None, None]
+    if need_w[0] or need_w[1]:
+        dzr = _raft_wgrad(ks, [h] + xsrc, gz, gr)
+        if need_w[0]:
+            dw[0] = dzr[:hidden].view(hidden, K, ks, ks)
+        if need_w[1]:
+            dw[1] = dzr[hidden:].view(hidden, K, ks, ks)
+    if need_w[2]:
+        dw[2] = _raft_wgrad(ks, [(_nchw(rh), hidden)] + xsrc, gq, None).view(hidden, K, ks, ks)
+    db = [None, None, None]
+    if any(need_b):                                          # column sums in double: at 3 x 10^4 pixels the fp32 partial rows of
+        sums = torch.empty(3, hidden, dtype=torch.float32, device=dev)             # the ConvGRU node sit at the rule's edge
+        ws = _WS.get("selgru_col_sum", get_lib().raw("stx_selgru_col_sum_workspace_floats")(P, hidden), dev)
+        _call("stx_selgru_col_sum", _p(gq), _p(gz), _p(gr), _p(sums), _p(ws), P, hidden)
+        db = [sums[k] if n else None for k, n in zip((1, 2, 0), need_b)]
+    return buf, dw, db
+
+
+def _raft_wgrad(ks, srcs, g0, g1):
+    """dW [(1 or 2) hidden][K][ks ks] of the source list against one or two dense gradient maps [B][H][W][hidden]."""
+    B, H, W, CG = g0.shape
+    if ks == 3:
+        return _convgru_wgrad(srcs, g0, g1, B, H, W)
+    K = sum(t.shape[1] for t, _ in srcs)
+    CC = CG if g1 is None else 2 * CG
+    n = get_lib().raw("stx_selgru_wgrad_workspace_floats")(B * H * W, K, CC)
+    if n <= 0:
+        raise StxError(f"raft_convgru: weight gradient of {K} x {CC} channels unsupported")
+    ws = _WS.get("selgru_wgrad", n, g0.device)
+    dw = torch.empty(CC, K, dtype=torch.float32, device=g0.device)
+    _call("stx_selgru_wgrad", *_src_args(srcs), _p(g0), _p(g1), CG, _p(dw), _p(ws), B * H * W)
+    return dw
+
+
+def _x_grads(buf, hidden, cx, need):
+    out, off = [], hidden
+    for c, n in zip(cx, need):
+        out.append(_nchw(buf[..., off:off + c]) if n else None)
+        off += c
+    return out
+
+
+class RaftConvGRU1x1Fn(torch.autograd.Function):
+    """h' = RaftConvGRU(h, x..) with 1x1 kernels as one node on csrc/selgru.hip; the chain of ConvGRUFn without context biases.
+    Saved: h and the x sources by reference, z, r, q and r h.  The last argument is the caller's grad mode (a forward always runs
+    with it switched off, and needs_input_grad follows requires_grad alone): without it r and q are not written."""
+
+    @staticmethod
+    def forward(ctx, h, wz, bz, wr, br, wq, bq, *xs):
+        *xs, track = xs
+        need = track and any(ctx.needs_input_grad)
+        hs = _cl_source(h.detach())
+        xsrc = [_cl_source(x.detach()) for x in xs]
+        z, r, q, rh, hn = _raft_cell_fwd(1, hs, xsrc, (wz, bz, wr, br, wq, bq), need)
+        if need:
+            ctx.save_for_backward(hs[0], z, r, q, rh, wz, wr, wq, *[t for t, _ in xsrc])
+            ctx.pitches = (hs[1], [p for _, p in xsrc])
+            ctx.has_b = [b is not None for b in (bz, br, bq)]
+        return _nchw(hn)
+
+    @staticmethod
+    def backward(ctx, g):
+        h, z, r, q, rh, wz, wr, wq, *xt = ctx.saved_tensors
+        hp, xp = ctx.pitches
+        need = ctx.needs_input_grad
+        hidden = h.shape[1]
+        need_b = [need[i] and has for i, has in zip((2, 4, 6), ctx.has_b)]
+        buf, dw, db = _raft_cell_bwd(1, _cl_source(g), (h, hp), z, r, q, rh, list(zip(xt, xp)), (wz, wr, wq), any(need[7:-1]),
+                                     [need[1], need[3], need[5]], need_b)
+        gh = _nchw(buf[..., :hidden]) if need[0] else None
+        return (gh, dw[0], db[0], dw[1], db[1], dw[2], db[2], *_x_grads(buf, hidden, [t.shape[1] for t in xt], need[7:-1]), None)
+
+
+class SelectiveConvGRUFn(torch.autograd.Function):
+    """h' = att small_gru(h, x..) + (1 - att) large_gru(h, x..) as one node.  Forward: the cell with 3x3 kernels first (both 1x1:
+    the large one), then the 1x1 cell, whose q epilogue forms the blend in place: neither cell's own state is kept.  Backward:
+    stx_selgru_blend_bwd (g_s, g_l and, if att wants it, g_att from the re-formed states), then the two cells' chains in the same
+    order; the second chain's last launch adds the first chain's [dL/dh | g_x] buffer as a second raw addend, so the sum has one
+    fixed order and autograd accumulates nothing.  Saved: h, att and the x sources by reference, z, r, q, r h of each cell."""
+
+    @staticmethod
+    def forward(ctx, att, h, *rest):
+        ws, wl, xs, track = rest[:6], rest[6:12], rest[12:-1], rest[-1]        # (track: the caller's grad mode, as above)
+        ks_s, ks_l = ws[0].shape[-1], wl[0].shape[-1]
+        need = track and any(ctx.needs_input_grad)
+        hs = _cl_source(h.detach())
+        xsrc = [_cl_source(x.detach()) for x in xs]
+        attc = att.detach().contiguous()
+        small_last = ks_s == 1
+        first, last = ((ks_l, wl), (ks_s, ws)) if small_last else ((ks_s, ws), (ks_l, wl))
+        f = _raft_cell_fwd(first[0], hs, xsrc, first[1], need)
+        l = _raft_cell_fwd(last[0], hs, xsrc, last[1], need, att=attc, other=f[4], blend=1 if small_last else 2)   # noqa: E741
+        if need:
+            ctx.save_for_backward(hs[0], attc, *f[:4], *l[:4], first[1][0], first[1][2], first[1][4], last[1][0], last[1][2],
+                                  last[1][4], *[t for t, _ in xsrc])
+            ctx.pitches = (hs[1], [p for _, p in xsrc])
+            ctx.small_last = small_last
+            ctx.ks = (first[0], last[0])
+            ctx.has_b = [[w[i] is not None for i in (1, 3, 5)] for w in (first[1], last[1])]
+        return _nchw(l[4])
+
+    @staticmethod
+    def backward(ctx, g):
+        h, att, zf, rf, qf, rhf, zl, rl, ql, rhl, wzf, wrf, wqf, wzl, wrl, wql, *xt = ctx.saved_tensors
+        hp, xp = ctx.pitches
+        need = ctx.needs_input_grad
+        B, hidden, H, W = h.shape
+        dev = h.device
+        P = B * H * W
+        gt, gp = _cl_source(g)
+        new = lambda: torch.empty(B, H, W, hidden, dtype=torch.float32, device=dev)       # noqa: E731
+        g_s, g_l = new(), new()
+        gatt = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev) if need[0] else None
+        (zs, qs), (zb, qb) = ((zl, ql), (zf, qf)) if ctx.small_last else ((zf, qf), (zl, ql))       # small cell, large cell
+        _call("stx_selgru_blend_bwd", _p(gt), gp, _p(att), _p(zs), _p(qs), _p(zb), _p(qb), _p(h), hp, _p(g_s), _p(g_l), _p(gatt),
+              P, hidden)
+        g_first, g_last = (g_l, g_s) if ctx.small_last else (g_s, g_l)
+        o_first, o_last = (8, 2) if ctx.small_last else (2, 8)               # where each cell's parameters sit in the inputs
+        xsrc = list(zip(xt, xp))
+        need_x = any(need[14:-1])
+        outs = [None] * len(need)
+        buf = None
+        for ks, gc, o, has_b, (z, r, q, rh), w in ((ctx.ks[0], g_first, o_first, ctx.has_b[0], (zf, rf, qf, rhf), (wzf, wrf, wqf)),
+                                                   (ctx.ks[1], g_last, o_last, ctx.has_b[1], (zl, rl, ql, rhl), (wzl, wrl, wql))):
+            need_b = [need[o + i] and hb for i, hb in zip((1, 3, 5), has_b)]
+            buf, dw, db = _raft_cell_bwd(ks, (_nchw(gc), hidden), (h, hp), z, r, q, rh, xsrc, w, need_x,
+                                         [need[o], need[o + 2], need[o + 4]], need_b, prev=buf)
+            outs[o:o + 6] = [dw[0], db[0], dw[1], db[1], dw[2], db[2]]
+        outs[0] = gatt
+        if need[1]:
+            outs[1] = _nchw(buf[..., :hidden])
+        outs[14:-1] = _x_grads(buf, hidden, [t.shape[1] for t in xt], need[14:-1])
+        return tuple(outs)
+
+
+def _raft_chk(who, h, x_list, cells):
+    """Argument checks of the RaftConvGRU ops; returns the kernel sizes of `cells` (tuples wz, bz, wr, br, wq, bq)."""
+    x_list = list(x_list)
+    if h is None or h.dim() != 4:
+        raise StxError(f"{who}: h must be a tensor [B, hidden, H, W]")
+    _convgru_chk(h, "h", who=who)
+    hidden = h.shape[1]
+    if not 1 <= len(x_list) <= CONVGRU_MAX_X:
+        raise StxError(f"{who}: {len(x_list)} x sources; 1..{CONVGRU_MAX_X} are served (4 sources with h)")
+    for i, x in enumerate(x_list):
+        _convgru_chk(x, f"x[{i}]", like=h, who=who)
+    cx = [int(x.shape[1]) for x in x_list]
+    K = hidden + sum(cx)
+    sizes = []
+    for cell in cells:
+        if len(cell) != 6 or cell[0] is None or cell[0].dim() != 4:
+            raise StxError(f"{who}: a cell is (wz, bz, wr, br, wq, bq) with weights [hidden, K, k, k]")
+        ks = int(cell[0].shape[-1])
+        if ks not in (1, 3):
+            raise StxError(f"{who}: kernel size {ks}; 1x1 and 3x3 cells are served")
+        for name, w, b in zip(("wz", "wr", "wq"), cell[0::2], cell[1::2]):
+            _convgru_chk(w, name, who=who)
+            _convgru_chk(b, "bias of " + name, who=who)
+            if w.dim() != 4 or tuple(w.shape) != (hidden, K, ks, ks):
+                raise StxError(f"{who}: {name} has shape {tuple(w.shape)}, expected {(hidden, K, ks, ks)}")
+            if b is not None and tuple(b.shape) != (hidden,):
+                raise StxError(f"{who}: bias of {name} has shape {tuple(b.shape)}, expected {(hidden,)}")
+        sizes.append(ks)
+    cx3 = cx + [0] * (3 - len(cx))
+    lib = get_lib()
+    if not (lib.raw("stx_selgru_supported")(hidden, len(cx), *cx3) and lib.raw("stx_convgru_supported")(hidden, len(cx), *cx3, 3)):
+        raise StxError(f"{who}: hidden {hidden} (a multiple of 16, <= {CONVGRU_MAX_HIDDEN}) with x channels {cx} (multiples of 4, "
+                       f"hidden + sum <= {CONVGRU_MAX_K}) is not served")
+    return sizes
+
+
+@fp32_region
+def raft_convgru(h, x_list, wz, bz, wr, br, wq, bq):
+    """RaftConvGRU of SelectiveStereo (reference SelectiveStereo/SelectiveRAFT/update.py:15-30) on the gfx950 kernels, one autograd
+    node: the ConvGRU cell without context biases, its kernel size (1 or 3) read from the weights.  For 3x3 it is
+    `convgru(h, None, None, None, x_list, ...)` to the bit; 1x1 runs on csrc/selgru.hip.  Shapes, strides, limits and refusals as
+    `convgru`."""
+    ks, = _raft_chk("raft_convgru", h, x_list, [(wz, bz, wr, br, wq, bq)])
+    if ks == 3:
+        return ConvGRUFn.apply(h, None, None, None, wz, bz, wr, br, wq, bq, *x_list)
+    return RaftConvGRU1x1Fn.apply(h, wz, bz, wr, br, wq, bq, *x_list, torch.is_grad_enabled())
+
+
+@fp32_region
+def selective_convgru(att, h, x_list, small, large):
+    """SelectiveConvGRU of SelectiveStereo (reference SelectiveStereo/SelectiveRAFT/update.py:61-71), one autograd node:
+        h' = att * RaftConvGRU_small(h, x..) + (1 - att) * RaftConvGRU_large(h, x..)
+    att [B, 1, H, W]; h, x_list as `convgru`; small / large = (wz, bz, wr, br, wq, bq) of the two cells, kernel sizes 1 or 3 read
+    from the weights, at least one of them 1 (the blend lives in the 1x1 kernel's epilogue).  The blend is formed in double from
+    the 1x1 cell's unrounded state and rounded once; neither cell's own state is materialised beyond the call.  Returns h' as an
+    NCHW view of channels-last storage, fp32.  Anything not served raises StxError and launches nothing."""
+    who = "selective_convgru"
+    small, large = tuple(small), tuple(large)
+    ks_s, ks_l = _raft_chk(who, h, x_list, [small, large])
+    if ks_s != 1 and ks_l != 1:
+        raise StxError(f"{who}: kernel sizes {ks_s} and {ks_l}; one of the two cells must be 1x1")
+    if att is None or att.dim() != 4:
+        raise StxError(f"{who}: att must be a tensor [B, 1, H, W]")
+    _convgru_chk(att, "att", like=h, channels=1, who=who)
+    return SelectiveConvGRUFn.apply(att, h, *small, *large, *x_list, torch.is_grad_enabled())
+
+
+# ------------------------------------------------------------------------------ contextual spatial attention (csa.hip)
+CSA_MAX_C = 256
+CSA_MAX_KERNEL = 7
+
+
+def _csa_chk(who, x, w1=None, w2=None, w_sam=None):
+    """Argument checks of the CSA ops; returns (B, C, H, W, kernel size or None)."""
+    for name, t in (("x", x), ("w1", w1), ("w2", w2), ("w_sam", w_sam)):
+        if t is None:
+            continue
+        if not on_device(t):
+            raise StxError(f"{who}: {name}: expected a ROCm device tensor, got {t.device} -- the attention has no CPU fallback")
+        if t.dtype != torch.float32:
+            raise StxError(f"{who}: {name}: expected float32, got {t.dtype}")
+        if t.dim() != 4:
+            raise StxError(f"{who}: {name} has shape {tuple(t.shape)}, expected 4 dims")
+    B, C, H, W = x.shape
+    k = None if w_sam is None else int(w_sam.shape[-1])
+    if min(B, H, W) < 1 or not get_lib().raw("stx_csa_supported")(C, 1 if k is None else k):
+        raise StxError(f"{who}: {C} channels (a multiple of 16, <= {CSA_MAX_C}) with a {k} x {k} kernel (odd, <= {CSA_MAX_KERNEL}) on "
+                       f"{tuple(x.shape)} is not served")
+    if w1 is not None and (tuple(w1.shape) != (C // 16, C, 1, 1) or w2 is None or tuple(w2.shape) != (C, C // 16, 1, 1)):
+        raise StxError(f"{who}: the MLP weights have shapes {tuple(w1.shape)} and {None if w2 is None else tuple(w2.shape)}, expected "
+                       f"{(C // 16, C, 1, 1)} and {(C, C // 16, 1, 1)}")
+    if w_sam is not None and tuple(w_sam.shape) != (1, 2, k, k):
+        raise StxError(f"{who}: w_sam has shape {tuple(w_sam.shape)}, expected {(1, 2, k, k)}")
+    return B, C, H, W, k
+
+
+def _csa_pool(xs, pitch, B, C, HW):
+    nblk = get_lib().raw("stx_csa_blocks")(HW, C)
+    dev = xs.device
+    psum = torch.empty(B, nblk, C, dtype=torch.float64, device=dev)
+    pmax = torch.empty(B, nblk, C, dtype=torch.float32, device=dev)
+    pidx = torch.empty(B, nblk, C, dtype=torch.int32, device=dev)
+    _call("stx_csa_pool", _p(xs), pitch, _p(psum), _p(pmax), _p(pidx), B, HW, C)
+    return nblk, psum, pmax, pidx
+
+
+def _csa_gate_state(B, C, dev):
+    return (torch.empty(B, C, dtype=torch.float32, device=dev), torch.empty(B, 2, C, dtype=torch.float64, device=dev),
+            torch.empty(B, C, dtype=torch.int32, device=dev))
+
+
+def _csa_sam_bwd(g, att, cmap, w, need_w):
+    """gmap [B][H][W][2] and dw [1][2][k][k] (None without need_w) from the gradient of att."""
+    B, _, H, W = att.shape
+    k = w.shape[-1]
+    dev = att.device
+    gc = g.contiguous()
+    gpre = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    gmap = torch.empty(B, H, W, 2, dtype=torch.float32, device=dev)
+    dw = torch.empty(1, 2, k, k, dtype=torch.float32, device=dev) if need_w else None
+    ws = _WS.get("csa_sam_bwd", get_lib().raw("stx_csa_sam_bwd_workspace_floats")(B, H, W, k), dev) if need_w else None
+    _call("stx_csa_sam_bwd", _p(gc), _p(att), _p(cmap), _p(w), _p(gpre), _p(gmap), _p(dw), _p(ws), B, H, W, k)
+    return gmap, dw
+
+
+def _csa_gate_bwd(pgate, nblk, gg, pooled, argp, w1, w2, gx, accumulate, need_w1, need_w2, need_x, HW):
+    """Backward of the MLP and of the two global pools; gx [B][H][W][C] receives (or is added) the pools' gradient."""
+    B, C = argp.shape
+    dev = argp.device
+    dw1 = torch.empty(C // 16, C, 1, 1, dtype=torch.float32, device=dev) if need_w1 else None
+    dw2 = torch.empty(C, C // 16, 1, 1, dtype=torch.float32, device=dev) if need_w2 else None
+    gavg = torch.empty(B, C, dtype=torch.float32, device=dev)
+    gmx = torch.empty(B, C, dtype=torch.float32, device=dev)
+    _call("stx_csa_gate_bwd", _p(pgate), nblk, _p(gg), _p(pooled), _p(w1), _p(w2), _p(dw1), _p(dw2), _p(gavg), _p(gmx), B, HW, C)
+    if need_x:
+        _call("stx_csa_pool_bwd", _p(gx), _p(gavg), _p(gmx), _p(argp), 1 if accumulate else 0, B, HW, C)
+    return dw1, dw2
+
+
+class CsaFn(torch.autograd.Function):
+    """(x', att) = (cam(x) x, sam(x')) in three launches (csrc/csa.hip); the backward pass in its fixed-order partials.  Saved: x by
+    reference, the gate, the pooled vectors (double), the two arg max maps (int32), the 2-channel map and att."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w_sam, track):
+        B, C, H, W = x.shape
+        k = w_sam.shape[-1]
+        dev = x.device
+        need = track and any(ctx.needs_input_grad)           # (track: the caller's grad mode, as in the cells)
+        xs, pitch = _cl_source(x.detach())
+        w1c, w2c, wsc = w1.detach().contiguous(), w2.detach().contiguous(), w_sam.detach().contiguous()
+        nblk, psum, pmax, pidx = _csa_pool(xs, pitch, B, C, H * W)
+        xp = torch.empty(B, H, W, C, dtype=torch.float32, device=dev)
+        cmap = torch.empty(B, H, W, 2, dtype=torch.float32, device=dev)
+        argc = torch.empty(B, H, W, dtype=torch.int32, device=dev) if need else None
+        gate, pooled, argp = _csa_gate_state(B, C, dev) if need else (None, None, None)
+        _call("stx_csa_apply", _p(xs), pitch, _p(psum), _p(pmax), _p(pidx), nblk, _p(w1c), _p(w2c), _p(xp), _p(cmap), _p(argc),
+              _p(gate), _p(pooled), _p(argp), B, H * W, C)
+        att = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+        _call("stx_csa_sam", _p(cmap), _p(wsc), _p(att), B, H, W, k)
+        if need:
+            ctx.save_for_backward(xs, gate, pooled, argp, argc, cmap, att, w1c, w2c, wsc)
+            ctx.pitch, ctx.nblk = pitch, nblk
+            ctx.set_materialize_grads(False)
+        return _nchw(xp), att
+
+    @staticmethod
+    def backward(ctx, gxp, gatt):
+        xs, gate, pooled, argp, argc, cmap, att, w1, w2, wsam = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        B, C, H, W = xs.shape
+        dev = xs.device
+        gmap = dws = None
+        if gatt is not None:
+            gmap, dws = _csa_sam_bwd(gatt, att, cmap, wsam, need[3])
+        if not any(need[:3]) or (gxp is None and gmap is None):
+            return None, None, None, dws, None
+        gs, gpitch = _cl_source(gxp) if gxp is not None else (None, 0)
+        gx = torch.empty(B, H, W, C, dtype=torch.float32, device=dev)
+        pgate = torch.empty(B, ctx.nblk, C, dtype=torch.float64, device=dev)
+        _call("stx_csa_apply_bwd", _p(xs), ctx.pitch, _p(gate), _p(gs), gpitch, _p(gmap), _p(argc), _p(gx), _p(pgate), B, H * W, C)
+        dw1, dw2 = _csa_gate_bwd(pgate, ctx.nblk, None, pooled, argp, w1, w2, gx, True, need[1], need[2], need[0], H * W)
+        return _nchw(gx) if need[0] else None, dw1, dw2, dws, None
+
+
+class CsaGateFn(torch.autograd.Function):
+    """gate = ChannelAttentionEnhancement(x) [B, C, 1, 1]: the pooled partials and a one-workgroup finish."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2):
+        B, C, H, W = x.shape
+        dev = x.device
+        xs, pitch = _cl_source(x.detach())
+        w1c, w2c = w1.detach().contiguous(), w2.detach().contiguous()
+        nblk, psum, pmax, pidx = _csa_pool(xs, pitch, B, C, H * W)
+        gate, pooled, argp = _csa_gate_state(B, C, dev)
+        _call("stx_csa_gate", _p(psum), _p(pmax), _p(pidx), nblk, _p(w1c), _p(w2c), _p(gate), _p(pooled), _p(argp), B, H * W, C)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(pooled, argp, w1c, w2c)
+            ctx.hw = (H, W)
+        return gate.view(B, C, 1, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        pooled, argp, w1, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        B, C = argp.shape
+        H, W = ctx.hw
+        gg = g.reshape(B, C).contiguous()
+        gx = torch.empty(B, H, W, C, dtype=torch.float32, device=argp.device) if need[0] else None
+        dw1, dw2 = _csa_gate_bwd(None, 0, gg, pooled, argp, w1, w2, gx, False, need[1], need[2], need[0], H * W)
+        return None if gx is None else _nchw(gx), dw1, dw2
+
+
+class CsaSpatialFn(torch.autograd.Function):
+    """att = SpatialAttentionExtractor(x) [B, 1, H, W]: the map sweep without a gate, then the k x k convolution."""
+
+    @staticmethod
+    def forward(ctx, x, w, track):
+        B, C, H, W = x.shape
+        k = w.shape[-1]
+        dev = x.device
+        need = track and any(ctx.needs_input_grad)
+        xs, pitch = _cl_source(x.detach())
+        wc = w.detach().contiguous()
+        cmap = torch.empty(B, H, W, 2, dtype=torch.float32, device=dev)
+        argc = torch.empty(B, H, W, dtype=torch.int32, device=dev) if need else None
+        _call("stx_csa_apply", _p(xs), pitch, None, None, None, 0, None, None, None, _p(cmap), _p(argc), None, None, None, B, H * W, C)
+        att = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+        _call("stx_csa_sam", _p(cmap), _p(wc), _p(att), B, H, W, k)
+        if need:
+            ctx.save_for_backward(argc, cmap, att, wc)
+            ctx.C = C
+        return att
+
+    @staticmethod
+    def backward(ctx, g):
+        argc, cmap, att, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        B, _, H, W = att.shape
+        gmap, dw = _csa_sam_bwd(g, att, cmap, w, need[1])
+        gx = None
+        if need[0]:
+            gx = torch.empty(B, H, W, ctx.C, dtype=torch.float32, device=att.device)
+            _call("stx_csa_apply_bwd", None, 0, None, None, 0, _p(gmap), _p(argc), _p(gx), None, B, H * W, ctx.C)
+        return None if gx is None else _nchw(gx), dw, None
+
+
+@fp32_region
+def csa_gate(x, w1, w2):
+    """ChannelAttentionEnhancement.forward of SelectiveStereo (reference SelectiveRAFT/update.py:106-121): sigmoid(fc(avgpool(x)) +
+    fc(maxpool(x))) with fc = w2 relu(w1 .), w1 [C/16, C, 1, 1], w2 [C, C/16, 1, 1]; returns [B, C, 1, 1] fp32.  x logical NCHW,
+    channels-last memory is read in place.  Served: C a multiple of 16 up to 256; anything else raises StxError."""
+    _csa_chk("csa_gate", x, w1, w2)
+    return CsaGateFn.apply(x, w1, w2)
+
+
+@fp32_region
+def csa_spatial(x, w):
+    """SpatialAttentionExtractor.forward (reference SelectiveRAFT/update.py:123-135): sigmoid(conv([mean_c x | max_c x], w)) with
+    w [1, 2, k, k], k odd up to 7, zero padding k // 2; returns [B, 1, H, W] fp32."""
+    _csa_chk("csa_spatial", x, w_sam=w)
+    return CsaSpatialFn.apply(x, w, torch.is_grad_enabled())
+
+
+@fp32_region
+def csa(x, w1, w2, w_sam):
+    """The contextual spatial attention of one context map (reference SelectiveIGEV/igev_stereo.py:225-226), fused:
+    x' = csa_gate(x, w1, w2) * x and att = csa_spatial(x', w_sam), to the bit, in three launches.  Returns (x' as an NCHW view of
+    channels-last storage, att [B, 1, H, W])."""
+    _csa_chk("csa", x, w1, w2, w_sam)
+    return CsaFn.apply(x, w1, w2, w_sam, torch.is_grad_enabled())
 
 
 class SharedInputConvsFn(torch.autograd.Function):
