@@ -797,6 +797,27 @@ int stx_monster_scale_shift(const float* mono, const float* gt, const unsigned c
 int stx_monster_apply_scale_shift(const float* x, const float* scale_shift, int with_shift, float* out, int B, long long n,
                                   void* stream);
 
+/* ---- instnorm.hip: instance normalisation + activation (+ residual tail), fp32 -------------------------------------------------
+ * nn.InstanceNorm2d / 3d with affine=False, track_running_stats=False, biased variance (the reference's IGEV BasicConv_IN /
+ * Conv2x_IN and the RAFT-family ResidualBlock).  `planes` = B C planes of S = H W or D H W floats each; layout 0 = every plane one
+ * contiguous run (NCHW / NCDHW), the only layout the kernels serve (a channels-last tensor goes through one copy in the binding).
+ *   xhat = (x - mean) / sqrt(var + eps);  y = act(xhat), or with skip (same shape): y = relu(skip + act(xhat)).
+ *   act: 0 none, 1 ReLU, 3 LeakyReLU(0.01).  S >= 2, S < 2^31.  x, skip, y, gy, gx, gskip 16-byte aligned.
+ * A plane is cut into chunks by a rule of (planes, S) alone: stx_instnorm_plan returns the chunks per plane and the path
+ *   (0: one chunk per plane, one launch; 1: two launches, per-chunk partial sums in the workspace, then apply).
+ *   stx_instnorm_ws_bytes: bytes of that workspace (8-byte aligned; 0 on path 0, -1 for arguments the kernels refuse).
+ * stx_instnorm_fwd: stats (NULL or [planes][2] DOUBLES: mean, 1 / sqrt(var + eps)) is what the backward needs besides x and skip.
+ *   The sums, the moments and the expression above are formed in double from the fp32 input and rounded once.
+ * stx_instnorm_bwd: gx = rstd (g' - mean(g') - xhat mean(g' xhat)), g' = gy [y > 0 with skip] act'(xhat); gskip = gy [y > 0].
+ *   Either may be NULL (gskip needs skip).  xhat and the masks are re-formed: y is not needed.  ReLU passes where its input is
+ *   > 0, LeakyReLU has slope 0.01 where xhat <= 0.  No float atomics: bitwise reproducible. */
+int stx_instnorm_plan(long long planes, long long S, int layout, int* chunks, int* path);
+long long stx_instnorm_ws_bytes(long long planes, long long S, int layout);
+int stx_instnorm_fwd(const float* x, const float* skip, float* y, void* stats, void* workspace, long long planes, long long S,
+                     int layout, int act, float eps, void* stream);
+int stx_instnorm_bwd(const float* gy, const float* x, const float* skip, const void* stats, float* gx, float* gskip, void* workspace,
+                     long long planes, long long S, int layout, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

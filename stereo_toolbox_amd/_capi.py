@@ -219,6 +219,11 @@ SIGNATURES = {
     "stx_bn_bwd_apply": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P],
     "stx_bn_bwd_reduce2": [_P] * 14 + [_L, _I, _I, _I, _P],
     "stx_bn_bwd_apply2": [_P] * 18 + [_L, _I, _I, _I, _P],
+    # instnorm.hip
+    "stx_instnorm_plan": [_L, _L, _I, _P, _P],
+    "stx_instnorm_ws_bytes": [_L, _L, _I],
+    "stx_instnorm_fwd": [_P, _P, _P, _P, _P, _L, _L, _I, _I, _F, _P],
+    "stx_instnorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
 }
 _RET_CHARP = ("stx_last_error", "stx_build_info")
 
@@ -246,7 +251,7 @@ class StxLib:
             fn = getattr(self._dll, name, None)
             if fn is None:
                 continue
-            fn.restype = ctypes.c_longlong if name.endswith(("_floats", "_stat_rows")) else _I
+            fn.restype = ctypes.c_longlong if name.endswith(("_floats", "_stat_rows", "_bytes")) else _I
             fn.argtypes = argtypes
             self._fns[name] = fn
 

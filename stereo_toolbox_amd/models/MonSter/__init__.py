@@ -4,3 +4,5 @@ from ..IGEVStereo.aggregation import FeatureAtt  # noqa: F401
 from ..IGEVStereo.geometry import Combined_Geo_Encoding_Volume  # noqa: F401
 from ..IGEVStereo.submodule import build_gwc_volume, context_upsample, upsample_disp_from_logits  # noqa: F401
 from ..IGEVStereo.update import ConvGRU  # noqa: F401
+from ..RAFTStereo.extractor import ResidualBlock  # noqa: F401
+from ..IGEVStereo.submodule import BasicConv_IN, Conv2x_IN  # noqa: F401

@@ -5,3 +5,5 @@ from ..update import (ChannelAttentionEnhancement, RaftConvGRU, SelectiveConvGRU
                       contextual_spatial_attention)
 from ...IGEVStereo import (Combined_Geo_Encoding_Volume, ConvGRU, build_gwc_volume, context_upsample,  # noqa: F401
                            disparity_regression, groupwise_correlation, upsample_disp_from_logits)
+from ...IGEVStereo.submodule import BasicConv_IN, Conv2x_IN  # noqa: F401
+from ...RAFTStereo.extractor import ResidualBlock  # noqa: F401

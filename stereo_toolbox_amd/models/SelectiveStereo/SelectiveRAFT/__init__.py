@@ -4,3 +4,5 @@ from ..update import (ChannelAttentionEnhancement, RaftConvGRU, SelectiveConvGRU
                       contextual_spatial_attention)
 from ...IGEVStereo import ConvGRU, context_upsample  # noqa: F401
 from ...RAFTStereo import CorrBlock1D, CorrBlockFast1D, PytorchAlternateCorrBlock1D, upsample_flow  # noqa: F401
+from ...IGEVStereo.submodule import BasicConv_IN, Conv2x_IN  # noqa: F401
+from ...RAFTStereo.extractor import ResidualBlock  # noqa: F401

@@ -4287,3 +4287,104 @@ def monster_align(mono, gt, mask=None):
     no Python loop, no host synchronisation).  Differentiable in mono with the fit held constant; returned in mono's dtype."""
     low = _low_dtype(mono)
     return _as_dtype(_monster_align(*_to_fp32((mono, gt)), mask), low)
+
+
+# --------------------------------------------------------------------------------------- instance norm + activation (+ residual tail)
+INSTNORM_ACTS = {"none": 0, "relu": 1, "lrelu": 3}                       # the codes of stx_act (csrc/stx_common.h)
+INSTNORM_MAX_PLANE = 1 << 31                                             # csrc/instnorm.hip: elements per plane, exclusive
+
+
+def instance_norm_plan(planes, S):
+    """(chunks per plane, path) the launchers of csrc/instnorm.hip take for `planes` planes of S elements: path 0 = one workgroup
+    per plane and one launch, 1 = per-chunk partial sums and an apply launch."""
+    chunks, path = ctypes.c_int(0), ctypes.c_int(0)
+    get_lib().call("stx_instnorm_plan", planes, S, 0, ctypes.byref(chunks), ctypes.byref(path))
+    return chunks.value, path.value
+
+
+def _instnorm_ws(planes, S, device):
+    nbytes = get_lib().raw("stx_instnorm_ws_bytes")(planes, S, 0)
+    if nbytes < 0:
+        raise StxError(f"instance_norm: {planes} planes of {S} elements are not served")
+    return _WS.get("instnorm", (nbytes + 7) // 8 * 2, device) if nbytes else None     # (an 8-byte aligned start: torch's allocations are)
+
+
+class InstanceNormFn(torch.autograd.Function):
+    """act(instance_norm(x)) or relu(skip + act(instance_norm(x))) on stx_instnorm_fwd / _bwd.  Saves x, skip and the per-plane
+    (mean, rstd) -- [B C][2] doubles; the output is not saved, the backward re-forms xhat and the masks."""
+
+    @staticmethod
+    def forward(ctx, x, skip, act, eps):
+        planes = x.shape[0] * x.shape[1]
+        S = x.numel() // planes
+        y = torch.empty_like(x)
+        grad = not isinstance(ctx, _NoCtx)
+        stats = torch.empty(planes, 2, dtype=torch.float64, device=x.device) if grad else None
+        _call("stx_instnorm_fwd", _p(x), _p(skip), _p(y), _p(stats), _p(_instnorm_ws(planes, S, x.device)), planes, S, 0, act, eps)
+        if grad:
+            ctx.save_for_backward(x, skip, stats)
+            ctx.act = act
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, skip, stats = ctx.saved_tensors
+        planes = x.shape[0] * x.shape[1]
+        S = x.numel() // planes
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gskip = torch.empty_like(skip) if skip is not None and ctx.needs_input_grad[1] else None
+        if gx is None and gskip is None:
+            return None, None, None, None
+        ws = _instnorm_ws(planes, S, x.device) if gx is not None else None
+        gy = _aligned16(gy.contiguous())                                  # (held until the launch is queued)
+        _call("stx_instnorm_bwd", _p(gy), _p(x), _p(skip), _p(stats), _p(gx), _p(gskip), _p(ws), planes, S, 0, ctx.act)
+        return gx, gskip, None, None
+
+
+def _instnorm_dense(t, name):
+    """Dense NCHW / NCDHW, 16-byte aligned, fp32, on the device -- the one layout the kernels serve."""
+    t = _aligned16(t.contiguous())
+    _chk(t, name)
+    return t
+
+
+@fp32_region
+def _instance_norm(x, skip, act, eps):
+    x, skip = _instnorm_dense(x, "x"), (None if skip is None else _instnorm_dense(skip, "skip"))
+    if torch.is_grad_enabled() and (x.requires_grad or (skip is not None and skip.requires_grad)):
+        return InstanceNormFn.apply(x, skip, act, eps)
+    return InstanceNormFn.forward(_NoCtx(), x, skip, act, eps)
+
+
+def instance_norm(x, act="none", eps=1e-5, skip=None):
+    """x [B, C, H, W] or [B, C, D, H, W] -> act(F.instance_norm(x, eps=eps)) with act "none", "relu" or "lrelu" (LeakyReLU(0.01));
+    with `skip` (x's shape, dtype and device) relu(skip + act(instance_norm(x))), the tail of the reference's ResidualBlock.  No
+    affine parameters, no running statistics, biased variance: nn.InstanceNorm2d / 3d as the reference constructs them, the same
+    in train and eval.  One autograd node, differentiable in x and skip; the output is not saved.  The sums, the moments and the
+    normalised value are formed in double and rounded once; no float atomics, bitwise reproducible.  A dense channels_last input
+    goes through one layout copy each way and the result comes back channels_last; other strides are made contiguous.  fp16 / bf16
+    inputs (also under autocast) are cast up and the result is returned in x's dtype."""
+    who = "instance_norm"
+    if act not in INSTNORM_ACTS:
+        raise StxError(f"{who}: act {act!r} is not one of {tuple(INSTNORM_ACTS)}")
+    if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+        raise StxError(f"{who}: x must be [B, C, H, W] or [B, C, D, H, W], got {tuple(getattr(x, 'shape', ()))}")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise StxError(f"{who}: empty tensor {tuple(x.shape)}")
+    if x.dtype != torch.float32 and x.dtype not in _LOW:
+        raise StxError(f"{who}: x must be float32, float16 or bfloat16, got {x.dtype}")
+    if not on_device(x):
+        raise StxError(f"{who}: expected a ROCm device tensor, got {x.device} -- there is no CPU fallback")
+    S = x.numel() // (x.shape[0] * x.shape[1])
+    if S < 2:
+        raise StxError(f"{who}: more than one value per plane is needed, got {tuple(x.shape)} (torch refuses it in training)")
+    if S >= INSTNORM_MAX_PLANE:
+        raise StxError(f"{who}: {S} elements per plane are not served (2^31 and above)")
+    if skip is not None and (not isinstance(skip, torch.Tensor) or skip.shape != x.shape or skip.dtype != x.dtype
+                             or skip.device != x.device):
+        raise StxError(f"{who}: skip must match x in shape, dtype and device: {tuple(x.shape)} {x.dtype} {x.device}, got "
+                       f"{tuple(getattr(skip, 'shape', ()))} {getattr(skip, 'dtype', None)} {getattr(skip, 'device', None)}")
+    low = _low_dtype(x)
+    cl = x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+    y = _as_dtype(_instance_norm(*_to_fp32((x, skip)), INSTNORM_ACTS[act], float(eps)), low)
+    return y.contiguous(memory_format=torch.channels_last) if cl else y
